@@ -750,6 +750,24 @@ def respawn_under_torchrun(n):
     os.execve(sys.executable, cmd, env)
 
 
+DUMP_BUDGET = 64 << 20   # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, det):
+    """--dump-outputs: the per-image detection arrays one timed step returned, (n_i, 6 + nm) each -- xyxy, confidence, class (+ mask
+    coefficients), highest confidence first -- as <out_dir>/det_<image>.npy in float32.  Should they exceed DUMP_BUDGET bytes, every image keeps
+    its leading rows within an equal share of it."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = [d.detach().float().cpu().numpy() for d in det]
+    if arrs and sum(v.nbytes for v in arrs) > DUMP_BUDGET:
+        rows = DUMP_BUDGET // len(arrs) // max(arrs[0].shape[1] * 4, 1)
+        arrs = [v[:rows] for v in arrs]
+    for i, v in enumerate(arrs):
+        np.save(os.path.join(out_dir, f"det_{i:04d}.npy"), v)
+
+
 def dry_run_tail(a, model, x, step, nm, dev, rank, world):
     """--dry-run-emu: the N-rank skeleton of main() without a GPU -- exactly K timed steps between fences, max over ranks, the DDP training
     probe (smart_DDP over gloo, loss * WORLD_SIZE, bucketed all-reduce of the gradient arena), rank 0 prints ONE JSON line with the keys the
@@ -760,11 +778,14 @@ def dry_run_tail(a, model, x, step, nm, dev, rank, world):
     clk.mark(0)
     ndet = 0
     for i in range(a.steps):
-        ndet += len(step())
+        last = step()
+        ndet += len(last)
         clk.mark(i + 1)
     fence(dev, world)
     dt = time.perf_counter() - t0
     assert ndet == a.steps * a.batch
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
     dt = reduce_max([dt], dev, world)[0]
     train = None
     if not a.no_train:
@@ -801,6 +822,8 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the secondary C4 / C5 lines and the NMS distributions")
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the untimed parity check of the timed plan against the CPU oracle")
     ap.add_argument("--op-table", default="", help="write the per-op timing table (JSON: in-situ and isolated ms, %% of bound) to this path")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (rank 0: one "
+                    "float32 array of detections per image) as DIR/<name>.npy; same arguments, same inputs")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -882,17 +905,20 @@ def main():
             evs[i + 1].record()
             host_t.append(time.perf_counter())
         if pipelined:
-            ndet += len(pipe.flush())
+            r = pipe.flush()   # the last step's per-image results
+            ndet += len(r)
         fence(dev, world)
         dt = time.perf_counter() - t0
         assert ndet == a.steps * a.batch, (ndet, a.steps, a.batch)  # every batch of the timed region delivered its per-image results inside it
         if os.environ.get("Y5_BENCH_DEBUG") and rank == 0:
             d = [round((host_t[i + 1] - host_t[i]) * 1e3, 2) for i in range(a.steps)]
             print(f"[bench debug] pipelined={pipelined} wall {dt * 1e3:.2f} ms, host ms per step: {d}", file=sys.stderr)
-        return dt, [evs[i].elapsed_time(evs[i + 1]) for i in range(a.steps)]
+        return dt, [evs[i].elapsed_time(evs[i + 1]) for i in range(a.steps)], r
 
-    dt, step_ms = timed_run(not a.sequential)
-    alt_dt, _ = timed_run(a.sequential)
+    dt, step_ms, last = timed_run(not a.sequential)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
+    alt_dt, _, _ = timed_run(a.sequential)
     dt, alt_dt = reduce_max([dt, alt_dt], dev, world)
 
     # ---- forward / NMS alone: device events, >= 50 iterations ------------------------------------------------------------------

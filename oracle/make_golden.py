@@ -6,7 +6,8 @@ oracle/ref_shim.py) on deterministic synthetic inputs (oracle/detgen.py).  Run i
     python -m oracle.make_golden            # rewrites tests/golden/
 
 Inputs and weights are NOT stored: they are regenerated from (name, seed) by detgen on any machine.
-Only expected outputs (full when small, strided samples + float64 checksums when large) are committed.
+Only expected outputs (full when small, strided samples + float64 checksums when large, or quantized with a
+recorded error bound that the tests subtract from their tolerance: gen_crosscheck) are committed.
 """
 from __future__ import annotations
 
@@ -613,6 +614,214 @@ def gen_ckpt(ns):
     print("ckpt", os.path.getsize(path), tuple(z.shape))
 
 
+XC_LABELS = [np.array([[2, 100.0, 120.0, 40.0, 60.0], [7, 300.5, 310.25, 80.0, 20.0]], np.float32), np.zeros((0, 5), np.float32),
+             np.array([[0, 50.0, 60.0, 30.0, 30.0]], np.float32)]
+
+
+def xc_metrics_batches():
+    """The four (detections, labels) batches of tests/test_oracle_vs_reference.py::test_process_batch_and_ap_match_live_reference (seed 77)."""
+    rng = np.random.default_rng(77)
+    out = []
+    for _ in range(4):
+        m = int(rng.integers(1, 25))
+        lab = np.zeros((m, 5), np.float32)
+        lab[:, 0] = rng.integers(0, 4, m)
+        xy = rng.uniform(0, 500, (m, 2)); wh = rng.uniform(10, 140, (m, 2))
+        lab[:, 1:3], lab[:, 3:5] = xy, xy + wh
+        pick = rng.integers(0, m, 90)
+        det = np.zeros((90, 6), np.float32)
+        det[:, :4] = lab[pick, 1:] + rng.normal(0, 5, (90, 4))
+        det[:, 4] = np.sort(rng.uniform(0, 1, 90))[::-1]
+        det[:, 5] = np.where(rng.uniform(0, 1, 90) < 0.8, lab[pick, 0], rng.integers(0, 4, 90))
+        out.append((det, lab))
+    return out
+
+
+def xc_train_setup():
+    """Data, weights and schedule of test_training_loop_restatement_matches_reference_pieces: (cfg, imgs, targets per image, bs, epochs, hyp)."""
+    import copy
+
+    from . import train_oracle as to
+
+    imgs, tpi = to.synthetic_set(8, 64, per_img=2, seed=6)
+    return copy.deepcopy(TINY_CFG), imgs, tpi, 4, 3, dict(to.HYP)
+
+
+XC_PARTS = {"loss": ("loss_", "ab_"), "tta": ("tta_",), "metrics": ("nms", "pb_", "ap_"), "train": ("train_",)}  # tests/golden/crosscheck_<part>.npz
+XC_TTA_Q = 1e-5     # quantization steps of the two large outputs, well below the tolerances their tests apply (1e-5 + 1e-5 |z|, 2e-5 + 2e-3 |w|)
+XC_TRAIN_Q = 4e-6
+
+
+def xc_quantize(ref, base, q):
+    """ref (float32) as integer steps of q above base: (k int32, the largest |base + k q - ref| in float64).  A test that holds a value to
+    atol + rtol |ref| holds it to (atol - (1 + rtol) err) + rtol |base + k q| instead: passing that implies the original bound exactly."""
+    d = (ref.astype(np.float64) - base) / q
+    assert np.abs(d).max() < 2 ** 31 - 1
+    k = np.round(d).astype(np.int32)
+    return k, np.array(np.abs(base + k.astype(np.float64) * q - ref.astype(np.float64)).max() if k.size else 0.0)
+
+
+def _i4_planes(a):
+    """int32 array -> its four byte planes, (4, last axis, ...): the high planes of small steps are runs of 0x00 / 0xff that zlib packs away."""
+    b = np.ascontiguousarray(np.moveaxis(a.astype("<i4"), -1, 0))
+    return np.ascontiguousarray(np.moveaxis(b.view(np.uint8).reshape(b.shape + (4,)), -1, 0))
+
+
+def _i4_unplanes(p):
+    b = np.ascontiguousarray(np.moveaxis(p, 0, -1)).view("<i4").reshape(p.shape[1:])
+    return np.moveaxis(b, 0, -1)
+
+
+def load_crosscheck(out_dir=OUT):
+    """The reference outputs gen_crosscheck stored, one dict over all crosscheck_<part>.npz files."""
+    G = {}
+    for part in XC_PARTS:
+        with np.load(os.path.join(out_dir, f"crosscheck_{part}.npz")) as f:
+            G.update({k[:-3] if k.endswith("#i4") else k: _i4_unplanes(f[k]) if k.endswith("#i4") else f[k] for k in f.files})
+    return G
+
+
+def gen_crosscheck(ns):
+    """tests/golden/crosscheck_<part>.npz: what the unmodified reference computes on the inputs of tests/test_oracle_vs_reference.py (inputs that
+    differ from the other fixtures) -- ComputeLoss.build_targets / loss / input gradients (yolov5s), four autobalance calls, the TTA forward (yolov5n),
+    NMS with and without a-priori labels, process_batch / ap_per_class, and three epochs of the train.py loop on the tiny model (per-iteration loss
+    items, final parameters and EMA).  Everything is stored exactly but the TTA output and the trained weights: those are quantized (xc_quantize;
+    the weights as steps above the seeded initial weights, the EMA as steps above the final weights) with the bound the tests subtract."""
+    import math
+
+    import yaml
+
+    from . import yolo_oracle as yo
+
+    G = {}
+    with open(os.path.join(ns.root, "data/hyps/hyp.scratch-low.yaml")) as f:
+        hyp_low = yaml.safe_load(f)
+
+    # ComputeLoss: build_targets, the loss and its input gradients
+    torch.manual_seed(0)
+    m = ns.yolo.DetectionModel(os.path.join(ns.root, "models/yolov5s.yaml"))
+    m.hyp = dict(hyp_low)
+    cl = ns.loss.ComputeLoss(m)
+    G["loss_anchors"] = m.model[-1].anchors.clone().numpy()
+    p = [torch.from_numpy(detgen.uniform((3, 3, s, s, 85), -3.0, 3.0, name=f"v{s}", seed=31)).requires_grad_(True) for s in (24, 12, 6)]
+    t = torch.from_numpy(detgen.synth_targets(3, 11, seed=31))
+    tcls, tbox, idx, anch = cl.build_targets(p, t)
+    for i in range(3):
+        G[f"loss_idx{i}"] = torch.stack(list(idx[i])).numpy()
+        G[f"loss_tcls{i}"], G[f"loss_tbox{i}"], G[f"loss_anch{i}"] = tcls[i].numpy(), tbox[i].numpy(), anch[i].numpy()
+    loss, items = cl(p, t)
+    loss.backward()
+    G["loss_loss"], G["loss_items"] = loss.detach().numpy(), items.numpy()
+    for i in range(3):
+        G[f"loss_grad{i}"] = p[i].grad.numpy()
+
+    # ComputeLoss(autobalance=True): losses and the balance list after each of four calls
+    m = ns.yolo.DetectionModel(os.path.join(ns.root, "models/yolov5s.yaml"), ch=3, nc=80)
+    m.hyp = dict(hyp_low)
+    cl = ns.loss.ComputeLoss(m, autobalance=True)
+    G["ab_ssi"], G["ab_anchors"] = np.array(cl.ssi), m.model[-1].anchors.clone().numpy()
+    for step in range(4):
+        p = [torch.from_numpy(detgen.uniform((2, 3, s, s, 85), -3.0, 3.0, name=f"ab{s}", seed=40 + step)) for s in (16, 8, 4)]
+        t = torch.from_numpy(detgen.synth_targets(2, 6, seed=40 + step))
+        loss, items = cl(p, t)
+        G[f"ab_loss{step}"], G[f"ab_items{step}"], G[f"ab_balance{step}"] = loss.numpy(), items.numpy(), np.array(cl.balance, np.float64)
+
+    # TTA forward
+    torch.manual_seed(0)
+    m = ns.yolo.DetectionModel(os.path.join(ns.root, "models/yolov5n.yaml"))
+    m.load_state_dict(yo.det_state_dict(yo.model_cfg("yolov5n"), 3, fused=False))
+    m.eval()
+    x = torch.from_numpy(detgen.uniform((2, 3, 96, 128), 0.0, 1.0, name="tta", seed=5))
+    with torch.no_grad():
+        G["tta_k"], G["tta_err"] = xc_quantize(m(x, augment=True)[0].numpy(), 0.0, XC_TTA_Q)
+    G["tta_q"] = np.array(XC_TTA_Q)
+
+    # NMS, plain and with a-priori labels
+    pred = detgen.synth_predictions(2, 1500, 85, obj_pow=3, seed=41)
+    with ref_shim.oracle_nms_mode():
+        for i, r in enumerate(ns.general.non_max_suppression(torch.from_numpy(pred), 0.25, 0.45, max_det=300)):
+            G[f"nms_{i}"] = r.numpy()
+    pred = detgen.synth_predictions(3, 800, 15, obj_pow=3, seed=43)
+    for ml in (False, True):
+        with ref_shim.oracle_nms_mode():
+            out = ns.general.non_max_suppression(torch.from_numpy(pred), 0.25, 0.45, labels=[torch.from_numpy(lb) for lb in XC_LABELS], multi_label=ml,
+                                                 max_det=300)
+        for i, r in enumerate(out):
+            G[f"nmslab{int(ml)}_{i}"] = r.numpy()
+
+    # process_batch / ap_per_class
+    iouv = torch.linspace(0.5, 0.95, 10)
+    stats = []
+    for i, (det, lab) in enumerate(xc_metrics_batches()):
+        ref = ns.metrics.process_batch(torch.from_numpy(det), torch.from_numpy(lab), iouv).numpy()
+        G[f"pb_{i}"] = ref
+        stats.append((ref, det[:, 4], det[:, 5], lab[:, 0]))
+    tp, conf, pcls, tcls = (np.concatenate(v, 0) for v in zip(*stats))
+    for i, a in enumerate(ns.metrics.ap_per_class(tp, conf, pcls, tcls, plot=False, names={})):
+        G[f"ap_{i}"] = np.asarray(a, np.float64)
+
+    # train.py:234-248,372-434 on the tiny model: DetectionModel (train mode), ComputeLoss, smart_optimizer, ModelEMA
+    cfg, imgs, tpi, bs, epochs, h = xc_train_setup()
+    torch.manual_seed(0)
+    m = ns.yolo.DetectionModel(cfg)
+    load_det_weights(m, 9)
+    init = yo.det_state_dict(cfg, 9, fused=False)   # what the test regenerates: must be the reference model's starting point, bit for bit
+    for k, v in m.state_dict().items():
+        if v.dtype.is_floating_point and not k.endswith("anchors"):
+            assert torch.equal(init[k].to(v.dtype), v), k
+    nbs, nb = 64, 2
+    accumulate = max(round(nbs / bs), 1)
+    h["weight_decay"] *= bs * accumulate / nbs
+    opt = ns.torch_utils.smart_optimizer(m, "SGD", h["lr0"], h["momentum"], h["weight_decay"])
+    lf = lambda x: ((1 - math.cos(x * math.pi / epochs)) / 2) * (h["lrf"] - 1) + 1  # noqa: E731  one_cycle(1, lrf, epochs)
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lf)
+    ema = ns.torch_utils.ModelEMA(m)
+    m.hyp = h
+    cl = ns.loss.ComputeLoss(m)
+    nw = max(round(h["warmup_epochs"] * nb), 100)
+    last, losses = -1, []
+    for epoch in range(epochs):
+        m.train()
+        opt.zero_grad()
+        for i in range(nb):
+            ids = list(range(i * bs, (i + 1) * bs))
+            ni = i + nb * epoch
+            x = imgs[ids].float() / 255
+            t = torch.cat([torch.cat((torch.full((len(tpi[j]), 1), float(k)), tpi[j][:, 1:]), 1) for k, j in enumerate(ids)], 0)
+            if ni <= nw:
+                accumulate = max(1, np.interp(ni, [0, nw], [1, nbs / bs]).round())
+                for j, g in enumerate(opt.param_groups):
+                    g["lr"] = np.interp(ni, [0, nw], [h["warmup_bias_lr"] if j == 0 else 0.0, g["initial_lr"] * lf(epoch)])
+                    g["momentum"] = np.interp(ni, [0, nw], [h["warmup_momentum"], h["momentum"]])
+            loss, items = cl(m(x), t)
+            loss.backward()
+            if ni - last >= accumulate:
+                torch.nn.utils.clip_grad_norm_(m.parameters(), max_norm=10.0)
+                opt.step()
+                opt.zero_grad()
+                ema.update(m)
+                last = ni
+            losses.append(items.detach().clone())
+        sched.step()
+    G["train_losses"], G["train_updates"] = torch.stack(losses).numpy(), np.array(ema.updates)
+    G["train_q"], err = np.array(XC_TRAIN_Q), 0.0
+    esd = ema.ema.state_dict()
+    for k, v in m.state_dict().items():
+        if v.dtype.is_floating_point and not k.endswith("anchors"):
+            base = init[k].numpy().astype(np.float64)
+            G[f"train_sd:{k}"], e1 = xc_quantize(v.numpy(), base, XC_TRAIN_Q)
+            G[f"train_ema:{k}"], e2 = xc_quantize(esd[k].numpy(), base + G[f"train_sd:{k}"] * XC_TRAIN_Q, XC_TRAIN_Q)
+            err = max(err, float(e1), float(e2))
+    G["train_err"] = np.array(err)
+    for part, prefixes in XC_PARTS.items():
+        path = os.path.join(OUT, f"crosscheck_{part}.npz")
+        planes = lambda v: v.dtype == np.int32 and v.size >= 1 << 16   # noqa: E731  (the TTA output; not the many small weight tensors)
+        np.savez_compressed(path, **{(k + "#i4" if planes(v) else k): (_i4_planes(v) if planes(v) else v) for k, v in G.items() if k.startswith(prefixes)})
+        print("crosscheck", part, os.path.getsize(path))
+    L = load_crosscheck()
+    assert L.keys() == G.keys() and all(L[k].dtype == G[k].dtype and np.array_equal(L[k], G[k]) for k in G)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ns = ref_shim.load()
@@ -625,6 +834,9 @@ def main():
         return 0
     if len(sys.argv) > 1 and sys.argv[1] == "ckpt":
         gen_ckpt(ns)
+        return 0
+    if len(sys.argv) > 1 and sys.argv[1] == "crosscheck":
+        gen_crosscheck(ns)
         return 0
     if len(sys.argv) > 1 and sys.argv[1] == "detset_x":  # only the yolov5x fixture
         gen_detset(ns, "yolov5x_1280", "models/yolov5x.yaml", 1280, 1, 4, 397, bn_gamma_scale=0.07, cal_scenes=3)
@@ -650,6 +862,7 @@ def main():
     gen_letterbox(ns)
     gen_ckpt(ns)
     gen_augment(ns)
+    gen_crosscheck(ns)
     sizes = {f: os.path.getsize(os.path.join(OUT, f)) for f in sorted(os.listdir(OUT))}
     print(sizes, sum(sizes.values()))
 

@@ -9,8 +9,8 @@ imports `cv2`, `torchvision` and the un-vendored `ultralytics>=8.4.118` pip pack
 supply restated implementations for the handful of third-party functions the hot path
 actually calls.  Those restatements live in `oracle/thirdparty.py`.
 
-`/root/reference` does not exist on the GPU box: only `oracle/make_golden.py` and the
-`-m "not gpu"` cross-check tests (skipped when the directory is absent) may use this file.
+`/root/reference` does not exist on the GPU box: only `oracle/make_golden.py` uses this file.  The tests
+compare against what it wrote under tests/golden/ and never import the reference themselves.
 """
 from __future__ import annotations
 

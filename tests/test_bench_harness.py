@@ -39,3 +39,33 @@ def test_bench_two_rank_dry_run_on_the_emulator():
     want = sum(-(-p_.numel() // 64) * 64 * 4 for p_ in DetectionModel("yolov5n.yaml").parameters())
     assert t["allreduce_bytes_per_step"] == want, (t["allreduce_bytes_per_step"], want)
     assert t["loss"] > 0 and t["images_per_sec"] > 0
+
+
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_repeat_identically(tmp_path):
+    """--dump-outputs: after the timed steps (exactly --steps of them) the per-image detections of the last one land in DIR as float32 .npy files;
+    two runs with the same arguments see the same inputs and write the same arrays."""
+    import numpy as np
+
+    env = dict(os.environ)
+    env.pop("RANK", None), env.pop("WORLD_SIZE", None), env.pop("LOCAL_RANK", None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run-emu", "--model", "yolov5n", "--batch", "2", "--imgsz", "64",
+               "--steps", "3", "--warmup", "1", "--no-train", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["step_ms"]["n"] == 3     # one step time per timed step
+        assert r["ms_per_step"] > 0 and abs(r["value"] - 2 * 3 / (r["ms_per_step"] * 3 * 1e-3)) < 0.02 * r["value"]
+        files = sorted(os.listdir(d))
+        assert files == ["det_0000.npy", "det_0001.npy"], files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 6 for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -276,9 +276,8 @@ def test_detect_loop_matches_oracle_pipeline():
         np.testing.assert_allclose(got.numpy()[:, 4:], e[:, 4:], rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/data/images"), reason="the reference's sample images are only in the build container")
-def test_detect_on_reference_sample_images_C1():
-    """BASELINE config C1 (plumbing): data/images/{bus,zidane}.jpg -> detect() end to end (PIL decode, device letterbox, yolov5n
+def test_detect_on_reference_sample_images_C1(golden_dir):
+    """BASELINE config C1 (plumbing): the reference's data/images/{bus,zidane}.jpg (copied to tests/golden/) -> detect() end to end (PIL decode, device letterbox, yolov5n
     forward, NMS, scale_boxes + round), small imgsz so the emulator finishes; against the oracle pipeline on the same decoded pixels."""
     import os
 
@@ -297,7 +296,7 @@ def test_detect_on_reference_sample_images_C1():
             b[:, 5:] += 1.0
     m = m.eval().fuse()
     sd_f = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    paths = [os.path.join("/root/reference/data/images", f) for f in ("bus.jpg", "zidane.jpg")]
+    paths = [os.path.join(golden_dir, f) for f in ("bus.jpg", "zidane.jpg")]
     out = detect(m, paths, imgsz=96, conf_thres=0.25, iou_thres=0.45, max_det=100)
     assert len(out) == 2
     from tests import detset
