@@ -364,6 +364,36 @@ int y5_loss_backward(const y5_loss_desc* d, const void* const* p, int nt, const 
 int y5_loss_targets_layout(const y5_loss_desc* d, int nt, int level, size_t offs[10], long long* cap);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * y5_seg_loss_forward / y5_seg_loss_backward -- utils/segment/loss.py:47-120 `ComputeLoss.__call__` + `single_mask_loss` and
+ * `build_targets` (:122-199) with its tidx / xywhn outputs; replaces the per-level x per-image Python loop of loss.py:88-103 and its
+ * `b.unique()` host sync.  The box / objectness / class terms are y5_loss_forward's kernels on rows of stride 5 + nc + nm.
+ * p[i]: (bs, na, ny[i], nx[i], 5+nc+nm) in det.dtype; proto: (bs, nm, mh, mw) in det.dtype; targets as y5_loss_forward.
+ * masks: at proto resolution (the caller resamples like loss.py:89-90), element type mask_dtype (Y5_F32 or Y5_U8);
+ *        overlap != 0: (bs, mh, mw) image-wise instance ids, gt = (masks[b] == tidx) with the positional tidx of loss.py:130-136;
+ *        overlap == 0: (nmask >= nt, mh, mw), gt = masks[target index] (loss.py:99).
+ *        May be NULL when nt == 0 (not read).
+ * forward:  out5 (device, 5 floats) = [loss = (lbox+lobj+lcls+lseg)*bs, lbox, lseg, lobj, lcls]         (loss.py:108-114)
+ * backward: dp[i] and dproto = d(loss * *grad_scale)/d(p[i], proto), shapes and dtype of the inputs, every element written;
+ *           coefficient gradients of duplicate cells are summed in ascending row order (y5_loss_backward's contract).
+ *           Needs the workspace of the matching forward untouched.  No host synchronisation, no float atomics: bit-repeatable.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  y5_loss_desc det;   /* detection fields (nc = classes, without the mask coefficients) */
+  int nm;             /* mask coefficients per row, 1..32 */
+  int mh, mw;         /* proto / mask resolution */
+  int overlap;        /* ComputeLoss(overlap=...) (segment/train.py:160) */
+  int mask_dtype;     /* Y5_F32 | Y5_U8 */
+  int nmask;          /* masks.shape[0] */
+} y5_seg_loss_desc;
+size_t y5_seg_loss_workspace_bytes(const y5_seg_loss_desc* d, int nt);   /* 0 on invalid descriptor */
+/* Byte offset of float obji[nl] (as y5_loss_obji_offset) inside the segmentation workspace; -1 on invalid descriptor. */
+long long y5_seg_loss_obji_offset(const y5_seg_loss_desc* d, int nt);
+int y5_seg_loss_forward(const y5_seg_loss_desc* d, const void* const* p, const void* proto, const float* targets, int nt,
+                        const void* masks, float* out5, void* workspace, size_t workspace_bytes, void* stream);
+int y5_seg_loss_backward(const y5_seg_loss_desc* d, const void* const* p, const void* proto, int nt, const void* masks,
+                         const float* grad_scale, void* const* dp, void* dproto, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * y5_process_mask -- utils/segment/general.py:25-51 `process_mask` (+ `crop_mask` :10-22) for ONE image:
  * protos (c, mh, mw) f16|f32 contiguous; instance i has c fp32 coefficients at masks_in + i*ld_m and an xyxy box (input
  * image pixels) at boxes + i*ld_b (both may point into the NMS output rows: ld = 6+nm).  out: (n, ih, iw) when

@@ -56,6 +56,13 @@ class LossDesc(C.Structure):
                 ("obj_pw", C.c_float), ("anchor_t", C.c_float), ("cp", C.c_float), ("cn", C.c_float), ("fl_gamma", C.c_float)]
 
 
+class SegLossDesc(C.Structure):
+    """y5_seg_loss_desc (include/yolov5_hip.h)."""
+
+    _fields_ = [("det", LossDesc), ("nm", C.c_int), ("mh", C.c_int), ("mw", C.c_int), ("overlap", C.c_int), ("mask_dtype", C.c_int),
+                ("nmask", C.c_int)]
+
+
 class FilterJob(C.Structure):
     """include/yolov5_hip.h: y5_filter_job (one filter re-pack / weight-gradient unpack of a multi-filter launch)."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("total", C.c_longlong)] + \
@@ -174,6 +181,12 @@ EXPORTS = {
     "y5_loss_backward": (C.c_int, [C.POINTER(LossDesc), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_loss_targets_layout": (C.c_int, [C.POINTER(LossDesc), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_longlong)]),
+    "y5_seg_loss_workspace_bytes": (C.c_size_t, [C.POINTER(SegLossDesc), C.c_int]),
+    "y5_seg_loss_obji_offset": (C.c_longlong, [C.POINTER(SegLossDesc), C.c_int]),
+    "y5_seg_loss_forward": (C.c_int, [C.POINTER(SegLossDesc), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "y5_seg_loss_backward": (C.c_int, [C.POINTER(SegLossDesc), C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_process_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "y5_process_mask_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MaskImg), C.c_int, C.c_int, C.c_int,

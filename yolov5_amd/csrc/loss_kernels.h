@@ -30,6 +30,7 @@ struct Y5LossLevel {
   long long cap;     // row capacity = 5*na*nt
   // workspace arrays of this level
   int* rb; int* ra; int* rgj; int* rgi; int* rcls; int* next;
+  int* rt;           // [cap] target index of the row (segmentation entry points only; null for the detection loss)
   float* tbox;       // [cap][4]
   float* anch;       // [cap][2]
   float* iou;        // [cap]   clamp(ciou, 0) rounded to p's dtype
@@ -88,7 +89,7 @@ __device__ __forceinline__ float y5_wave_sum(float v) {
 }
 
 // ---- K1 -------------------------------------------------------------------------------------------------
-struct Y5Cand { bool ok; int b, a, cls, gj, gi; float tb[4]; };
+struct Y5Cand { bool ok; int b, a, cls, gj, gi, t; float tb[4]; };
 
 __device__ __forceinline__ Y5Cand y5_loss_candidate(const Y5LossParams& p, const Y5LossLevel& L, long long c) {
   Y5Cand r;
@@ -115,6 +116,7 @@ __device__ __forceinline__ Y5Cand y5_loss_candidate(const Y5LossParams& p, const
   r.ok = ok;
   if (!ok) return r;
   r.b = tb;
+  r.t = t;
   r.cls = tc;
   r.a = a;
   int gi = (int)(gx - ox), gj = (int)(gy - oy);                                          // loss.py:238 (.long() truncates)
@@ -153,6 +155,7 @@ void y5_loss_build_targets_kernel(const Y5LossParams p) {
     L.rb[row] = r.b; L.ra[row] = r.a; L.rgj[row] = r.gj; L.rgi[row] = r.gi; L.rcls[row] = r.cls;
     L.tbox[row * 4 + 0] = r.tb[0]; L.tbox[row * 4 + 1] = r.tb[1]; L.tbox[row * 4 + 2] = r.tb[2]; L.tbox[row * 4 + 3] = r.tb[3];
     L.anch[row * 2 + 0] = L.anchors[r.a * 2]; L.anch[row * 2 + 1] = L.anchors[r.a * 2 + 1];
+    if (L.rt) L.rt[row] = r.t;
     ++row;
   }
 }

@@ -88,6 +88,8 @@ class TrainEngine:
         self.gflat = self.be.empty((max(off, 64),), torch.float32)
         self.be.zero_(self.gflat)
         self.raw = {}
+        self.seg = False
+        self.proto = None
         self.convs = []
         self._dw_total = 0
         self._keep = []
@@ -119,6 +121,8 @@ class TrainEngine:
                 self.convs.append(st)
             elif op["op"] == "decode":
                 self.raw[op["level"]] = None  # allocated per forward: the caller owns the returned maps (models/yolo.py:98)
+            elif op["op"] == "to_nchw":
+                self.seg = True  # Segment head: the forward also returns proto (models/yolo.py:150)
         self.dz = self.be.empty((max(max_z, 8),), f16)
         self.dwflat = self.be.empty((max(self._dw_total, 64),), torch.float32)  # packed fp32 dW accumulators of all convs
         self.ws = self.be.empty((max(max_ws, 256),), torch.uint8)
@@ -323,11 +327,15 @@ class TrainEngine:
                 else:
                     _lib.check(lib.y5_train_glue_f32(0, _vp(self._ptr(lg)), _vp(be.ptr(self.raw[op["level"]])), B, op["ny"] * op["nx"], op["na"], op["no"],
                                                      self._ld(lg), 0, 0, stm), lib)
+            elif kind == "to_nchw":  # Proto output (bs, nm, mh, mw), NCHW like the reference's
+                s = op["src"]
+                self.proto = be.empty((B, s.C, s.H, s.W), self.dtype)
+                _lib.check(lib.y5_nhwc_to_nchw(_vp(self._ptr(s)), self.dt, _vp(be.ptr(self.proto)), B, s.C, s.H, s.W, self._ld(s), stm), lib)
             else:
                 raise NotImplementedError(kind)
         if self._nbt:
             torch._foreach_add_(self._nbt, 1)  # BatchNorm2d.num_batches_tracked of every layer: one launch instead of 57
-        return [self.raw[i] for i in sorted(self.raw)]
+        return [self.raw[i] for i in sorted(self.raw)] + ([self.proto] if self.seg else [])
 
     def _fwd_conv(self, st, stm):
         lib, be, B = self.lib, self.be, self.spec.B
@@ -521,6 +529,12 @@ class TrainEngine:
                 self._bwd_conv(op["_st"], stm, is_written, mark, grads, hold)
             elif kind == "to_nhwc":
                 pass
+            elif kind == "to_nchw":  # dproto (NCHW) -> NHWC gradient of proto.cv3's output; Proto's input (the P3 feature) then fans in with Detect level 0
+                s = op["src"]
+                dph, dpp, ddt = be.input(dps[len(self.raw)])
+                hold.append(dph)
+                _lib.check(lib.y5_nchw_to_nhwc(_vp(dpp), ddt, _vp(self._ptr(s, True)), self.dt, B, s.C, s.H, s.W, self._ld(s), 1.0, stm), lib)
+                mark(s)
             else:
                 raise NotImplementedError(kind)
         if self._unpack_pending:
@@ -743,7 +757,8 @@ class _TrainFn(torch.autograd.Function):
 
 
 def train_forward(model, x):
-    """Train-mode `BaseModel._forward_once` (models/yolo.py:160-170): list of (bs, na, ny, nx, no) fp16 tensors."""
+    """Train-mode `BaseModel._forward_once` (models/yolo.py:160-170): list of (bs, na, ny, nx, no) tensors; for a Segment head
+    (p, proto) with proto (bs, nm, mh, mw) (models/yolo.py:150)."""
     # fp32 images -> the fp32 plan (reference-precision mode: train.py without AMP); fp16 / uint8 images -> the fp16 (AMP) plan
     dtype = torch.float32 if x.dtype == torch.float32 else torch.float16
     key = (tuple(x.shape), str(x.device), dtype)
@@ -754,4 +769,5 @@ def train_forward(model, x):
         eng = TrainEngine(model, tuple(x.shape), x.device, dtype=dtype)
         cache[key] = eng
     eng.grad_sink = model.__dict__.get("_ddp_sink")
-    return list(_TrainFn.apply(eng, x, *eng.params))
+    outs = list(_TrainFn.apply(eng, x, *eng.params))
+    return (outs[:-1], outs[-1]) if eng.seg else outs  # Segment: (p, proto) (models/yolo.py:150)

@@ -24,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from .loss import ComputeLoss
+from .segment_loss import ComputeLoss as SegComputeLoss
 from .torch_utils import ModelEMA, de_parallel, smart_DDP, smart_optimizer
 
 HYP_SCRATCH_LOW = {  # data/hyps/hyp.scratch-low.yaml
@@ -103,12 +104,20 @@ def host_amp_step(optimizer, parameters, scaler, max_norm=10.0):
 
 
 def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_lr=False, amp=True, ema=True, world_size=1, rank=-1,
-          optimizer_name="SGD", max_norm=10.0, start_epoch=0, on_batch_end=None, nbs=64, val_loader=None, noval=False, sync_bn=False):
+          optimizer_name="SGD", max_norm=10.0, start_epoch=0, on_batch_end=None, nbs=64, val_loader=None, noval=False, sync_bn=False,
+          overlap=True):
     """Runs `epochs` epochs over `loader` (iterable of (imgs uint8|float BCHW, targets (nt, 6), *rest), re-iterable, len() = batches
     per epoch).  Returns dict(model, ema, optimizer, scheduler, scaler, mloss per epoch, losses per iteration, lr per epoch).
     rank / world_size as train.py's RANK / WORLD_SIZE (-1 / 1: single process; otherwise torch.distributed is initialised and the
     model is wrapped by smart_DDP).  val_loader: validated once per epoch on rank -1 / 0 with the EMA model (train.py:440-455 -> val_loop.run;
-    noval: only after the final epoch); sync_bn: train.py:269-271 (`--sync-bn` under DDP: BatchNorm statistics over the global batch); `results` per validated epoch = (P, R, mAP@.5, mAP@.5:.95, val box / obj / cls loss), `fitness` beside it."""
+    noval: only after the final epoch); sync_bn: train.py:269-271 (`--sync-bn` under DDP: BatchNorm statistics over the global batch); `results` per validated epoch = (P, R, mAP@.5, mAP@.5:.95, val box / obj / cls loss), `fitness` beside it.
+    Segment model (segment/train.py): the segmentation ComputeLoss(model, overlap=overlap) (:160,324), batch[4] = masks (:355,381), loss items
+    (lbox, lseg, lobj, lcls); mask-mAP validation is not implemented (val_loader raises)."""
+    from .yolo import Segment
+
+    seg = isinstance(de_parallel(model).model[-1], Segment)
+    if seg and val_loader is not None:
+        raise NotImplementedError("train_loop.train: validation of a segmentation model (mask mAP, segment/val.py) is not implemented")
     hyp = dict(HYP_SCRATCH_LOW if hyp is None else hyp)
     device = torch.device(device) if device is not None else next(model.parameters()).device
     nb = len(loader)
@@ -125,7 +134,7 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
         model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model).to(device)
     model.hyp = hyp                                                                 # :331
     ddp = smart_DDP(model) if rank != -1 and world_size > 1 else model              # :322
-    compute_loss = ComputeLoss(model)                                               # :352
+    compute_loss = SegComputeLoss(model, overlap=overlap) if seg else ComputeLoss(model)  # :352 (segment/train.py:324)
     nw = max(round(hyp["warmup_epochs"] * nb), 100)                                 # :341
     last_opt_step = -1
     scheduler.last_epoch = start_epoch - 1                                          # :347
@@ -135,7 +144,7 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
     best_fitness = 0.0
     for epoch in range(start_epoch, epochs):
         model.train()
-        mloss = torch.zeros(3, device=device)
+        mloss = torch.zeros(4 if seg else 3, device=device)
         if rank != -1 and hasattr(getattr(loader, "sampler", None), "set_epoch"):
             loader.sampler.set_epoch(epoch)                                         # :365
         optimizer.zero_grad()
@@ -155,7 +164,10 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
             else:     # fp32 plan (train.py without AMP): float32 images select it (train_engine.train_forward)
                 x = imgs.float() / 255 if imgs.dtype == torch.uint8 else imgs.float()
             pred = ddp(x)                                                           # :399
-            loss, loss_items = compute_loss(pred, targets.to(device))               # :400
+            if seg:
+                loss, loss_items = compute_loss(pred, targets.to(device), batch[4].to(device))  # segment/train.py:381
+            else:
+                loss, loss_items = compute_loss(pred, targets.to(device))           # :400
             if rank != -1:
                 loss = loss * world_size                                            # :401-402
             # the scale is FROZEN for all micro-batches of an accumulation window (GradScaler only changes it in update(), right after
@@ -196,8 +208,9 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
                 hist["results"].append(tuple(float(v) for v in results))
                 hist["fitness"].append(fi)
     scaler.update(block=True)
-    hist["losses"] = torch.stack(hist["losses"]).float().cpu() if hist["losses"] else torch.zeros(0, 3)
-    hist["mloss"] = torch.stack(hist["mloss"]).float().cpu() if hist["mloss"] else torch.zeros(0, 3)
+    ni_ = 4 if seg else 3
+    hist["losses"] = torch.stack(hist["losses"]).float().cpu() if hist["losses"] else torch.zeros(0, ni_)
+    hist["mloss"] = torch.stack(hist["mloss"]).float().cpu() if hist["mloss"] else torch.zeros(0, ni_)
     return dict(model=de_parallel(ddp), ema=ema_obj, optimizer=optimizer, scheduler=scheduler, scaler=scaler, best_fitness=best_fitness, **hist)
 
 
