@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 typedef enum { Y5_OK = 0, Y5_ERR_BAD_ARG = -1, Y5_ERR_UNSUPPORTED = -2, Y5_ERR_RUNTIME = -3, Y5_ERR_WORKSPACE = -4 } y5_status;
-typedef enum { Y5_F16 = 0, Y5_F32 = 1, Y5_U8 = 2 } y5_dtype;
+typedef enum { Y5_F16 = 0, Y5_F32 = 1, Y5_U8 = 2, Y5_I32 = 3 } y5_dtype;   /* Y5_I32: ground-truth masks of y5_val_match_masks only */
 
 int y5_version(void);                /* 10000*major + 100*minor + patch */
 const char* y5_last_error(void);     /* thread-local message of the last non-zero return */
@@ -451,6 +451,30 @@ int y5_letterbox_batch(const y5_letterbox_job* jobs_dev, int B, int H, int W, in
 int y5_val_match(const float* det, int ld_det, int max_det, const int* det_count, int bs, const float* labels, int ld_lab,
                  int nlabels, int img_col, int cls_col, int box_col, int xywh, const float* scale, const float* iouv, int niou,
                  unsigned char* correct, float* predn, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * y5_val_match_masks -- the mask branch of process_batch (utils/metrics.py:239-249, masks=True; mask_iou of ultralytics.utils.metrics,
+ * call site :250) for every image of a batch, as segment/val.py:287-304 runs it per image; no host synchronisation, no float atomics.
+ * det/det_count/max_det/bs: the padded NMS rows as in y5_val_match, boxes in LETTERBOXED pixels (process_mask gets pred[:, :4] before
+ *            scale_boxes, segment/val.py:289); max_det <= 1024.
+ * labels:    (nlabels, ld_lab) fp32; img_col (< 0: every row belongs to image 0) and cls_col are the only columns read.
+ * gt_masks:  overlap != 0: (bs, gh, gw) index maps, value k + 1 = the k-th label of that image in row order (values above the image's label
+ *            count select nothing); overlap == 0: (nlabels, gh, gw), non-zero = foreground, one plane per label row.  gt_dtype Y5_U8,
+ *            Y5_I32 or Y5_F32.  (gh, gw) != (mh, mw): resized bilinearly (align_corners=False) to (mh, mw), then > 0.5 (:246-248).
+ * predicted bits, exactly one of:
+ *   protos (bs, nm, mh, mw) Y5_F16|Y5_F32 + the nm coefficient columns 6.. of the rows: process_mask(upsample=False) (utils/segment/
+ *            general.py:25-51) for input images of ih x iw pixels, fused -- bit for bit y5_process_mask_batch(upsample=0);
+ *   pred_masks (bs, max_det, mh, mw) uint8, non-zero = foreground (pass protos = NULL).
+ * iouv (niou <= 32) / correct (bs, max_det, niou) uint8: as y5_val_match; rows past det_count are written as 0.  IoU over exact integer
+ *            pixel counts, (float)inter / ((float)(a + b - inter) + 1e-7f) -- the reference's fp32 value; tie rule as y5_val_match.
+ * workspace: >= y5_val_match_masks_ws_bytes(bs, max_det, nlabels) bytes of device memory, 4-byte aligned (Y5_ERR_WORKSPACE otherwise).
+ * Y5_ERR_UNSUPPORTED when mh * ceil(mw / 64) > 4096 (the prediction bitmap lives in LDS).
+ * ------------------------------------------------------------------------------------------------------- */
+long long y5_val_match_masks_ws_bytes(int bs, int max_det, int nlabels);
+int y5_val_match_masks(const float* det, int ld_det, int max_det, const int* det_count, int bs, const float* labels, int ld_lab,
+                       int nlabels, int img_col, int cls_col, const void* gt_masks, int gt_dtype, int overlap, int gh, int gw,
+                       const void* protos, int proto_dtype, int nm, const unsigned char* pred_masks, int mh, int mw, int ih, int iw,
+                       const float* iouv, int niou, unsigned char* correct, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * y5_scale_boxes_batch -- utils/general.py:613-626 `scale_boxes` (+ `clip_boxes` :629-640) applied IN PLACE to columns 0..3 of

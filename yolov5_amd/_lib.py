@@ -27,7 +27,7 @@ def disabled(name):
 
 LIB_PATH = os.environ.get("Y5_LIB_PATH") or os.path.join(_HERE, "libyolov5_hip.so")  # override: kernel experiments only
 
-Y5_F16, Y5_F32, Y5_U8 = 0, 1, 2
+Y5_F16, Y5_F32, Y5_U8, Y5_I32 = 0, 1, 2, 3
 Y5_OK, Y5_ERR_BAD_ARG, Y5_ERR_UNSUPPORTED, Y5_ERR_RUNTIME, Y5_ERR_WORKSPACE = 0, -1, -2, -3, -4   # y5_status (include/yolov5_hip.h)
 NMS_MULTI_LABEL, NMS_AGNOSTIC = 1, 2
 
@@ -195,6 +195,10 @@ EXPORTS = {
     "y5_letterbox_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "y5_val_match": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y5_val_match_masks_ws_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "y5_val_match_masks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_scale_boxes_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "y5_plan_create": (C.c_void_p, []),
     "y5_plan_destroy": (None, [C.c_void_p]),

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/yolov5_hip.h"
+#include "mask_value.h"
 #include "y5_common.h"
 #include "y5_host.h"
 
@@ -60,23 +61,7 @@ void y5_process_mask_kernel(const MaskParams p) {
   for (int i = tid; i < ww * wh; i += 256) {
     const int ly = i / ww, lx = i - ly * ww;
     const int gy = wy0 + ly, gx = wx0 + lx;
-    const float r = (float)gx, cc = (float)gy;
-    float v = 0.f;
-    if (r >= x1 && r < x2 && cc >= y1 && cc < y2) {  // crop_mask, general.py:22
-      float s = 0.f;
-      const TP* q = P + (long long)gy * p.mw + gx;
-      int k = 0;
-      for (; k + 8 <= p.c; k += 8) {   // eight prototype planes in flight (round 6; same order of additions)
-        TP t[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) t[e] = q[(k + e) * plane];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += s_coef[k + e] * (float)t[e];
-      }
-      for (; k < p.c; ++k) s += s_coef[k] * (float)q[k * plane];
-      v = 1.0f / (1.0f + expf(-s));
-    }
-    s_m[i] = v;
+    s_m[i] = y5_mask_lowres(P, plane, p.mw, p.c, s_coef, gx, gy, x1, y1, x2, y2);
   }
   __syncthreads();
   TO* out = static_cast<TO*>(p.out) + (long long)inst * p.oh * p.ow;
@@ -209,23 +194,7 @@ void y5_process_mask_batch_kernel(const MaskBatchParams p) {
     for (int i = tid; i < ww * wh; i += 256) {
       const int ly = i / ww, lx = i - ly * ww;
       const int gy = wy0 + ly, gx = wx0 + lx;
-      const float r = (float)gx, cc = (float)gy;
-      float v = 0.f;
-      if (r >= x1 && r < x2 && cc >= y1 && cc < y2) {  // crop_mask, general.py:22
-        float s = 0.f;
-        const TP* q = P + (long long)gy * p.mw + gx;
-        int k = 0;
-        for (; k + 8 <= p.c; k += 8) {   // eight prototype planes in flight (the plain loop waits for every load before the next: a latency chain of c round trips)
-          TP t[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) t[e] = q[(k + e) * plane];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) s += s_coef[k + e] * (float)t[e];   // (same order of additions as the plain loop)
-        }
-        for (; k < p.c; ++k) s += s_coef[k] * (float)q[k * plane];
-        v = 1.0f / (1.0f + expf(-s));
-      }
-      s_m[i] = v;
+      s_m[i] = y5_mask_lowres(P, plane, p.mw, p.c, s_coef, gx, gy, x1, y1, x2, y2);   // crop + sigmoid (mask_value.h)
     }
     __syncthreads();
 #pragma unroll 1
@@ -349,3 +318,4 @@ extern "C" int y5_process_mask(const void* protos, int proto_dtype, int c, int m
   }
   return y5_check_launch("y5_process_mask");
 }
+#include "seg_val.h"   // y5_val_match_masks: the mask branch of validation matching (same flags as the mask kernels above)

@@ -1,10 +1,12 @@
 """Validation metrics with the reference's names.
 
 Device side (one HIP launch per batch, `csrc/metrics.hip` -> `y5_val_match`):
-    process_batch(detections, labels, iouv)            utils/metrics.py:224-265 (box branch)
+    process_batch(detections, labels, iouv, ...)       utils/metrics.py:224-265, box branch and (masks=True, `y5_val_match_masks`) mask branch
     match_batch(out, counts, targets, shapes, iouv)    val.py:282-307 for all images of a batch: de-letterbox of the
                                                         predictions and labels fused with the matching
     ValStats                                            the `stats` list of val.py:218,308 kept on the device
+    match_masks_batch(out, counts, protos, targets,     segment/val.py:287-308 mask matching for all images of a batch, the predicted
+                      masks, iouv, overlap, shape)      masks computed from the prototypes inside the matcher (never written)
 Host side -- numpy, as in the reference (SURVEY keeps `ap_per_class` on the CPU: it runs once per epoch on a few
 thousand rows): `ap_per_class`, `compute_ap`, `smooth`, `fitness`.
 """
@@ -27,9 +29,11 @@ def _need_gpu(t, what):
         raise RuntimeError(f"yolov5_amd.metrics.{what} needs GPU tensors (no CPU path)")
 
 
-def process_batch(detections, labels, iouv):
+def process_batch(detections, labels, iouv, pred_masks=None, gt_masks=None, overlap=False, masks=False):
     """utils/metrics.py:224-265: detections (N,6+) [x1,y1,x2,y2,conf,cls], labels (M,5) [cls,x1,y1,x2,y2], iouv (niou)
-    -> bool (N, niou) on the device.  Tie rule and the equivalence with the reference's sort are in csrc/metrics.hip."""
+    -> bool (N, niou) on the device.  Tie rule and the equivalence with the reference's sort are in csrc/metrics.hip.
+    masks=True: the mask branch (:239-249) -- pred_masks (N, mh, mw) 0/1, gt_masks (M, gh, gw) 0/1 or, with overlap, one (1, gh, gw) / (gh, gw)
+    index map (value k + 1 = label k); the ground truth is resized to (mh, mw) when the shapes differ (`y5_val_match_masks`, loaded bits)."""
     _need_gpu(detections, "process_batch")
     n = detections.shape[0]
     niou = iouv.numel()
@@ -37,6 +41,13 @@ def process_batch(detections, labels, iouv):
         return torch.zeros((0, niou), dtype=torch.bool, device=detections.device)
     if n > 1024:
         raise ValueError("process_batch: at most 1024 detections per image")
+    if masks:
+        pm = pred_masks.to(detections.device)
+        pm = (pm if pm.dtype == torch.uint8 else (pm != 0).to(torch.uint8)).contiguous()
+        gt = gt_masks if not overlap or gt_masks.dim() == 3 else gt_masks[None]
+        correct = _match_masks(detections.float().contiguous()[None], None, labels.float().contiguous(), -1, 0, gt, overlap, iouv,
+                               pred_masks=pm[None])
+        return correct[0].bool()
     det = detections.float().contiguous()
     lab = labels.float().contiguous()
     iv = iouv.to(device=det.device, dtype=torch.float32).contiguous()
@@ -75,6 +86,65 @@ def match_batch(out, counts, targets, shapes, iouv, predn=False):
                           _p(correct), _p(pn), _lib.stream(dev))
     _lib.check(rc, lib)
     return (correct, pn) if predn else correct
+
+
+def _gt_masks(masks, dev):
+    m = masks.to(dev)
+    if m.dtype == torch.bool:
+        m = m.to(torch.uint8)
+    elif m.dtype not in (torch.uint8, torch.int32, torch.float32):
+        m = m.float()
+    return m.contiguous(), {torch.uint8: _lib.Y5_U8, torch.int32: _lib.Y5_I32, torch.float32: _lib.Y5_F32}[m.dtype]
+
+
+def _match_masks(det, counts, labels, img_col, cls_col, gt_masks, overlap, iouv, protos=None, shape=None, pred_masks=None):
+    """One y5_val_match_masks call: det (bs, max_det, ld) fp32 contiguous; either protos (bs, nm, mh, mw) and the letterboxed input `shape`
+    (computed bits) or pred_masks (bs, max_det, mh, mw) uint8 (loaded bits).  Returns correct (bs, max_det, niou) uint8."""
+    bs, max_det, ld = det.shape
+    dev = det.device
+    lib = _lib.lib()
+    iv = iouv.to(device=dev, dtype=torch.float32).contiguous()
+    niou = iv.numel()
+    gt, gdt = _gt_masks(gt_masks, dev)
+    gh, gw = gt.shape[-2:]
+    nl = labels.shape[0]
+    if nl and gt.shape[0] != (bs if overlap else nl):
+        raise ValueError(f"match_masks: {gt.shape[0]} ground-truth masks, expected {bs if overlap else nl} ({'overlap' if overlap else 'per instance'})")
+    ws = lib.y5_val_match_masks_ws_bytes(bs, max_det, nl)
+    if ws < 0:
+        _lib.check(int(ws), lib)
+    work = torch.empty(((ws + 3) // 4,), dtype=torch.int32, device=dev)
+    correct = torch.empty((bs, max_det, niou), dtype=torch.uint8, device=dev)
+    cn = counts.to(device=dev, dtype=torch.int32) if counts is not None else None
+    if protos is not None:
+        pr = protos if protos.dtype in (torch.float16, torch.float32) else protos.float()
+        pr = pr.contiguous()
+        nm, mh, mw = pr.shape[1:]
+        src = (_p(pr), _lib.Y5_F16 if pr.dtype == torch.float16 else _lib.Y5_F32, nm, None, mh, mw, int(shape[0]), int(shape[1]))
+    else:
+        mh, mw = pred_masks.shape[-2:]
+        src = (None, 0, 0, _p(pred_masks), mh, mw, 1, 1)
+    rc = lib.y5_val_match_masks(_p(det), ld, max_det, _p(cn), bs, _p(labels) if nl else None, labels.shape[1] if labels.dim() == 2 else 1, nl,
+                                img_col, cls_col, _p(gt) if nl else None, gdt, 1 if overlap else 0, gh, gw, *src, _p(iv), niou, _p(correct),
+                                _p(work), work.numel() * 4, _lib.stream(dev))
+    _lib.check(rc, lib)
+    return correct
+
+
+def match_masks_batch(out, counts, protos, targets, masks, iouv, overlap, shape):
+    """The mask branch of segment/val.py:282-308 for the whole batch in one C-ABI call (`y5_val_match_masks`, computed bits):
+    process_mask(proto, pred[:, 6:], pred[:, :4], shape) (upsample=False) fused with process_batch(..., masks=True) -- no predicted mask is written.
+
+    out (bs, max_det, 6+nm) / counts (bs): the padded NMS result (boxes in letterboxed pixels, before scale_boxes); protos (bs, nm, mh, mw)
+    f16|f32; targets (M, 6) [img, cls, ...] (only the image and the class are read); masks: (bs, gh, gw) index maps with overlap, else
+    (M, gh, gw) 0/1 in target order, uint8 / int32 / float32; shape: the letterboxed input (h, w).  Returns correct (bs, max_det, niou) uint8,
+    rows past counts 0."""
+    _need_gpu(out, "match_masks_batch")
+    dev = out.device
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        out = out.float().contiguous()
+    tg = targets.to(device=dev, dtype=torch.float32).contiguous()
+    return _match_masks(out, counts, tg, 0, 1, masks, overlap, iouv, protos=protos, shape=shape)
 
 
 class ValStats:
