@@ -7,19 +7,22 @@ N GPUs: one process per GPU (torch.distributed, backend nccl = RCCL), every rank
 (images are independent: weak scaling, no data-path collective -- DESIGN.md section "multi-GPU").
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run
-(one rank per GPU, 127.0.0.1 rendezvous); under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.  At N > 1 the line
-also carries the DDP TRAINING step (`train`: the only path with a collective -- bucketed RCCL all-reduce of the gradient arena
+(one rank per GPU, 127.0.0.1 rendezvous); under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.  With --full at N > 1 the
+line also carries the DDP TRAINING step (`train`: the only path with a collective -- bucketed RCCL all-reduce of the gradient arena
 overlapped with backward, train.py:404-405 semantics) with `rccl_ranks` and the all-reduce bytes per step.
 
 Protocol: >= 10 warm-up + >= 50 timed steps; `value` = images of the K timed steps / wall time between two
 barrier + synchronize fences (max over ranks); per-step device-event times give median / p10 / p90 beside it.  The K steps run through
 `DetectPipeline` (same kernels; the host's wait for batch i's per-image counts is taken after batch i+1 is queued, the NMS chain of batch i
-runs on a high-priority side stream beside forward i+1, the last batch is collected inside the timed region); `--sequential` times the plain loop, and whichever is not the headline is reported as
-`alt_step_mode` from a second timed run of the same K steps.
+runs on a high-priority side stream beside forward i+1, the last batch is collected inside the timed region); `--sequential` times the plain loop.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (all conv launches of one forward, durations
-measured IN SITU: one HIP event between consecutive plan ops of a real forward) and `cpu_baseline` (the CPU oracle = port of
-the reference path, timed on this box's host cores BEFORE the GPU work starts).
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, and print ONE JSON line on rank 0
+(contract in the task statement; `step_ms`, `detections_per_img` and the plan's provenance in `config` ride along).  `--full` adds everything
+else, after the timed steps and never inside them: `alt_step_mode` (a second timed run of the same K steps in the step mode that is not the
+headline), forward / NMS alone, `roofline` (all conv launches of one forward, durations measured IN SITU: one HIP event between consecutive plan
+ops of a real forward; measured ceilings and `value_at_ref_clock`), `gpu_state`, `pipeline`, `selfcheck`, `nms_distributions`, `configs`
+(C4 / C5), `train`, --op-table, and `cpu_baseline` (the CPU oracle = port of the reference path, timed on this box's host cores BEFORE the GPU
+work starts).  The --no-* switches leave parts of that out.
 """
 from __future__ import annotations
 
@@ -768,10 +771,46 @@ def dump_outputs(out_dir, det):
         np.save(os.path.join(out_dir, f"det_{i:04d}.npy"), v)
 
 
+def headline(a, world, dt, step_ms, ncand):
+    """The keys of the result line every run prints: the K timed steps (wall time `dt`, max over ranks; per-step event times `step_ms`)."""
+    imgs = a.batch * world * a.steps
+    return {
+        "metric": "images/sec at 640px (yolov5s bs=64), forward+NMS", "value": round(imgs / dt, 1), "unit": "images/sec",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+        "config": {"workload": f"{a.model} inference bs={a.batch}/GPU 3x{a.imgsz}x{a.imgsz} fp16: HIP forward (backbone+neck+Detect) + HIP NMS "
+                               "(conf 0.25, iou 0.45, max_det 1000) + per-image result lists; random-init weights, Detect biases calibrated to a realistic NMS load",
+                   "step_mode": "sequential: non_max_suppression(model(x)[0]) per step, host sync inside every step" if a.sequential else
+                                "DetectPipeline: the kernels of the sequential step; the host waits for batch i's counts after batch i+1 is queued (one-deep "
+                                "deferred collect, last batch flushed inside the timed region) and the NMS chain of batch i runs on a high-priority side stream "
+                                "beside forward i+1",
+                   "global_batch": a.batch * world, "parallelism": f"replicas x{world} (images independent, no data-path collective)"
+                                                                   + ("; the DDP training step with its RCCL all-reduce is the `train` object" if a.full else "")},
+        "step_ms": stats(step_ms), "detections_per_img": round(ncand, 1)}
+
+
+def plan_provenance(model):
+    """Which plan the timed steps ran (two lines are comparable only when plan_sha16 agrees), the kernel sources it was
+    built from and where its tile choices came from -- read from the live model, no launches."""
+    from yolov5_amd import engine as _eng
+
+    out = {}
+    try:
+        eng = next(iter(model._engines.values()))
+        out["plan_sha16"] = plan_hash((eng.engines[0] if getattr(eng, "parts", 1) > 1 else eng).plan_table())
+    except Exception:
+        out["plan_sha16"] = None
+    out["kernel_src_sha16"] = kernel_src_hash()
+    swaps = [list(s) for e in getattr(model, "_engines", {}).values() for s in getattr(e, "insitu_swaps", [])]
+    out["tile_choices"] = {"from_shipped_db": _eng.TUNE_STATS["db_entries"], "races_run_here": _eng.TUNE_STATS["races"], "in_situ_swaps": swaps}
+    return out
+
+
 def dry_run_tail(a, model, x, step, nm, dev, rank, world):
     """--dry-run-emu: the N-rank skeleton of main() without a GPU -- exactly K timed steps between fences, max over ranks, the DDP training
     probe (smart_DDP over gloo, loss * WORLD_SIZE, bucketed all-reduce of the gradient arena), rank 0 prints ONE JSON line with the keys the
-    driver parses.  Sequential step only (DetectPipeline needs HIP streams)."""
+    driver parses.  Sequential step only (DetectPipeline needs HIP streams).  It measures nothing, so it has no plain / --full split: the
+    training probe -- the N-rank path that --full takes on GPUs -- runs unless --no-train, since exercising it is what this mode is for."""
     fence(dev, world)
     clk = StepClock(dev, a.steps)
     t0 = time.perf_counter()
@@ -812,19 +851,24 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="images per GPU")
     ap.add_argument("--imgsz", type=int, default=640)
     ap.add_argument("--model", default="yolov5s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything besides the headline: the other "
+                    "step mode, forward / NMS alone, roofline and per-kernel figures, pipeline, selfcheck, NMS distributions, configs C4 / C5, the "
+                    "training step; and the CPU baseline before the GPU work")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--sequential", action="store_true", help="time the plain per-step loop (host sync inside every step) instead of DetectPipeline")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step measurement")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the detect/val pipeline measurement")
-    ap.add_argument("--train", action="store_true", help="(kept for compatibility: the training step is measured at every N unless --no-train)")
+    ap.add_argument("--no-train", action="store_true", help="(--full; --dry-run-emu) skip the training-step measurement")
+    ap.add_argument("--no-pipeline", action="store_true", help="(--full) skip the detect/val pipeline measurement")
+    ap.add_argument("--train", action="store_true", help="(kept for compatibility: with --full the training step is measured at every N unless --no-train)")
     ap.add_argument("--dry-run-emu", action="store_true", help="HARNESS TEST ONLY (tests/test_bench_harness.py): the rank logic of this file on the CPU "
                     "emulator over gloo with a tiny model -- respawn, rank env, fence, max-over-ranks, DDP train probe, rank-0 JSON; the numbers mean nothing")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary C4 / C5 lines and the NMS distributions")
-    ap.add_argument("--no-selfcheck", action="store_true", help="skip the untimed parity check of the timed plan against the CPU oracle")
-    ap.add_argument("--op-table", default="", help="write the per-op timing table (JSON: in-situ and isolated ms, %% of bound) to this path")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the secondary C4 / C5 lines and the NMS distributions")
+    ap.add_argument("--no-selfcheck", action="store_true", help="(--full) skip the untimed parity check of the timed plan against the CPU oracle")
+    ap.add_argument("--op-table", default="", help="(--full) write the per-op timing table (JSON: in-situ and isolated ms, %% of bound) to this path")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (rank 0: one "
                     "float32 array of detections per image) as DIR/<name>.npy; same arguments, same inputs")
     a = ap.parse_args()
+    if a.op_table and not a.full:
+        ap.error("--op-table needs --full (the per-op table is one of its measurements)")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         respawn_under_torchrun(a.gpus)
@@ -836,11 +880,12 @@ def main():
     emu = a.dry_run_emu
     assert emu or torch.cuda.is_available(), "bench.py needs a GPU"
 
-    # ---- CPU baseline first: the GPU is idle while the host cores run the oracle, the rest of the run is GPU work ------------
+    # ---- CPU baseline first (--full): the GPU is idle while the host cores run the oracle, the rest of the run is GPU work -----
     cpu = None
     if not a.no_cpu_baseline and world == 1 and not emu:
-        cpu = cpu_baseline()
-        torch.set_num_threads(min(8, usable_cores()))
+        if a.full:
+            cpu = cpu_baseline()
+        torch.set_num_threads(min(8, usable_cores()))   # (the host threads the timed steps run with, baseline or not)
 
     if emu:
         from tests.hipemu import backend as emu_backend
@@ -918,6 +963,18 @@ def main():
     dt, step_ms, last = timed_run(not a.sequential)
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, last)
+    if not a.full:
+        dt = reduce_max([dt], dev, world)[0]
+        if rank == 0:
+            res = headline(a, world, dt, step_ms, ncand)
+            res["config"].update(plan_provenance(model))
+            print(json.dumps(res))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below runs after the timed steps and never changes `value` -----------------------------------------
     alt_dt, _, _ = timed_run(a.sequential)
     dt, alt_dt = reduce_max([dt, alt_dt], dev, world)
 
@@ -1103,24 +1160,14 @@ def main():
             dom_busy = {"value": fam_rows[k_best][0], "kernel": k_best[:120], "launches_per_forward": fam_rows[k_best][1]}
     if rank == 0:
         imgs = a.batch * world * a.steps
-        res = {
-            "metric": "images/sec at 640px (yolov5s bs=64), forward+NMS", "value": round(imgs / dt, 1), "unit": "images/sec",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": f"{a.model} inference bs={a.batch}/GPU 3x{a.imgsz}x{a.imgsz} fp16: HIP forward (backbone+neck+Detect) + HIP NMS "
-                                   "(conf 0.25, iou 0.45, max_det 1000) + per-image result lists; random-init weights, Detect biases calibrated to a realistic NMS load",
-                       "step_mode": "sequential: non_max_suppression(model(x)[0]) per step, host sync inside every step" if a.sequential else
-                                    "DetectPipeline: the kernels of the sequential step; the host waits for batch i's counts after batch i+1 is queued (one-deep "
-                                    "deferred collect, last batch flushed inside the timed region) and the NMS chain of batch i runs on a high-priority side stream "
-                                    "beside forward i+1",
-                       "global_batch": a.batch * world, "parallelism": f"replicas x{world} (images independent, no data-path collective); "
-                                                                       "the DDP training step with its RCCL all-reduce is the `train` object"},
+        res = headline(a, world, dt, step_ms, ncand)
+        res.update({
             "alt_step_mode": {"mode": "DetectPipeline" if a.sequential else "sequential", "ms_per_step": round(alt_dt / a.steps * 1e3, 4),
                               "images_per_sec": round(imgs / alt_dt, 1)},
-            "step_ms": stats(step_ms), "forward_ms": round(fwd_ms, 4), "forward_ms_stats": stats(fwd), "nms_ms": round(nms_ms, 4),
+            "forward_ms": round(fwd_ms, 4), "forward_ms_stats": stats(fwd), "nms_ms": round(nms_ms, 4),
             "nms_ms_stats": stats(nms), "nms_us_per_img": round(nms_ms * 1e3 / a.batch, 2),
             "nms_device_ms": round(_pct(nms_dev, 0.5), 4), "nms_device_us_per_img": round(_pct(nms_dev, 0.5) * 1e3 / a.batch, 2),
-            "forward_images_per_sec": round(a.batch / (fwd_ms * 1e-3), 1), "detections_per_img": round(ncand, 1),
+            "forward_images_per_sec": round(a.batch / (fwd_ms * 1e-3), 1),
             # arithmetic intensity of the conv stack at this config = algorithmic flops / algorithmic bytes (144 flop/B for
             # yolov5s bs=64 640^2) is below the ridge (2500 TF / 8 TB/s = 312 flop/B): the stack as a whole is HBM-bound;
             # the MFMA view of the same launches is kept beside it
@@ -1157,7 +1204,7 @@ def main():
                          "conv_ms_per_step": round(conv_ms * parts, 4), "conv_ms_per_step_isolated": round(conv_ms_iso * parts, 4),
                          "launches_per_step": nconv * parts, "other_kernels_ms_per_step": round(other_ms * parts, 4),
                          "measured_ceilings": ceil},
-        }
+        })
         try:  # which plan the tuner built on this box: two lines are comparable only when this hash agrees
             res["config"]["plan_sha16"] = plan_sha16
             res["config"]["kernel_src_sha16"] = kernel_src_hash()

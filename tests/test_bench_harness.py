@@ -69,3 +69,11 @@ def test_bench_dump_outputs_repeat_identically(tmp_path):
         dumps.append(arrs)
     for f in dumps[0]:
         assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def test_bench_op_table_needs_full(tmp_path):
+    """The per-op table is a --full measurement: asked for on a plain run, bench.py refuses before any work instead of quietly skipping it."""
+    out = tmp_path / "ops.json"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--op-table", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--op-table needs --full" in p.stderr, (p.returncode, p.stderr[-2000:])
+    assert not out.exists()
