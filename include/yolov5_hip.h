@@ -577,6 +577,26 @@ typedef struct {
 int y5_mosaic_batch(const y5_mosaic_job* jobs_dev, int B, int S, int pad_value, void* dst, int dst_dtype, int div255, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * y5_polygon_masks -- the mask half of the segmentation input pipeline for a whole batch: utils/segment/dataloaders.py:180-199
+ * (`polygons2masks_overlap` / `polygons2masks` of ultralytics.data.utils, i.e. per instance np.asarray(polygon, int32) ->
+ * cv2.fillPoly(zeros(H, W), [pts], 1) -> cv2.resize to (H / ratio, W / ratio)), the mask flips of :212-223 and collate_fn's
+ * torch.cat of :298.  Kernels: csrc/seg_data.h.
+ * xy: (poly_off[n_inst], 2) float64 pixel coordinates (truncated toward zero on the device), instance i owns points
+ * poly_off[i] .. poly_off[i + 1]; inst_img: (n_inst) image of every instance, NON-DECREASING (label order inside an image);
+ * flip: (B, 2) {up-down, left-right} or NULL.  area: (n_inst) pixel count of every shrunk mask; order: (n_inst) for every image the
+ * permutation of ITS instances (local indices) that sorts by area, largest first -- as np.argsort(-areas) of the reference's uint64
+ * areas does, a ZERO area sorts FIRST; equal areas: lower label index first (the reference's order is unspecified there).
+ * overlap = 0: masks (n_inst, h, w) of 0 / 1 in label order.  overlap = 1: masks (B, h, w), pixel = 1 + rank of the last instance
+ * in that order that covers it, 0 = background; Y5_U8 holds up to 255 instances per image (the caller's check), Y5_F32 any number.
+ * ws: y5_polygon_masks_ws_bytes(n_inst, H, W, ratio) bytes, 256-byte aligned.  Three launches on `stream`, no host synchronisation.
+ * H * ceil(W / 32) * 4 bytes of LDS per workgroup: Y5_ERR_UNSUPPORTED beyond 160 KiB (about 1100 x 1100).
+ * ------------------------------------------------------------------------------------------------------- */
+size_t y5_polygon_masks_ws_bytes(int n_inst, int H, int W, int ratio);
+int y5_polygon_masks(const double* xy, const int* poly_off, const int* inst_img, int n_inst, int B, int H, int W, int ratio, int overlap,
+                     const unsigned char* flip, void* masks, int mask_dtype, int* order, long long* area, void* ws, size_t ws_bytes,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Execution plan: a recorded list of the calls above, replayed by ONE host call (and optionally through a
  * captured hipGraph).  Replaces the Python module walk of models/yolo.py:160-170 `_forward_once`.
  * ------------------------------------------------------------------------------------------------------- */

@@ -21,6 +21,7 @@
 #include "y5_common.h"
 #include "y5_host.h"
 #include "resize_u8.h"
+#include "seg_data.h"   // y5_polygon_masks: the mask half of the segmentation input pipeline
 
 namespace {
 struct AugParams {

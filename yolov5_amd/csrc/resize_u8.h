@@ -71,4 +71,16 @@ __device__ inline void resized_pixel(const unsigned char* src, int h0, int w0, i
     }
   }
 }
+// one-channel twin of resized_pixel whose source pixel is COMPUTED -- src(y, x) -> 0..255 -- instead of loaded (seg_data.h: the bits of a
+// rasterised polygon).  Same geometry, same taps, same fixed-point arithmetic, same exact-2x rule.
+template <typename F>
+__device__ inline int resized_value(int h0, int w0, const ResizeGeom& g, int yy, int xx, F&& src) {
+  if (!g.resize) return src(yy, xx);
+  if (g.area2) return (src(2 * yy, 2 * xx) + src(2 * yy, 2 * xx + 1) + src(2 * yy + 1, 2 * xx) + src(2 * yy + 1, 2 * xx + 1) + 2) >> 2;
+  const Axis ax = axis_x(xx, g.sx, w0);
+  const Axis ay = axis_y(yy, g.sy, h0);
+  const int h0v = src(ay.s0, ax.s0) * ax.w0 + src(ay.s0, ax.s1) * ax.w1;
+  const int h1v = src(ay.s1, ax.s0) * ax.w0 + src(ay.s1, ax.s1) * ax.w1;
+  return (((ay.w0 * (h0v >> 4)) >> 16) + ((ay.w1 * (h1v >> 4)) >> 16) + 2) >> 2;
+}
 }  // namespace

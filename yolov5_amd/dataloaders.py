@@ -8,8 +8,12 @@ rates of this engine (3 k img/s per GPU) the reference's 8 cv2 worker processes 
 
 Random draws follow the reference's ORDER per sample (documented in `draw_sample`), so that a `random.seed()` / `np.random.seed()`-ed
 run consumes the generators exactly as `__getitem__` does; they can also be passed in (parity tests).
-Not covered: rect batches / augment = False (the validation loader: augmentations.letterbox_batch), copy_paste, albumentations,
-perspective != 0, segments."""
+Segmentation datasets (utils/segment/dataloaders.py:130-301 `LoadImagesAndLabelsAndMasks`, utils/segment/augmentations.py:14-91): the
+second half of this file -- `draw_sample_seg`, `seg_mosaic_batch`, `SegMosaicLoader`, `seg_letterbox_batch`, `SegValLoader`.  The image half
+is the SAME `y5_mosaic_batch` launch; the polygons go through the reference's own float64 expressions on the host and ONE `y5_polygon_masks`
+call (csrc/seg_data.h) rasterises, shrinks, orders and flips the masks of the batch.
+Not covered: rect batches / augment = False of detection datasets (the validation loader: augmentations.letterbox_batch), copy_paste,
+albumentations, perspective != 0."""
 from __future__ import annotations
 
 import ctypes as C
@@ -176,6 +180,58 @@ def _finish_labels(t, d, width, height):
     return res
 
 
+def _fill_job(j, images, d, s):
+    """Geometry half of one job of the y5_mosaic_batch table (tiles, rectangles, inverse affine map) -> (hw, rects, pads, M, width, height)."""
+    hw = []
+    for t, i in enumerate(d["indices"]):
+        im = images[i]
+        if not (_lib.accepts(im) and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
+            raise ValueError("mosaic_batch: images must be uint8 (h, w, 3) device tensors with contiguous rows")
+        h0, w0 = int(im.shape[0]), int(im.shape[1])
+        rh, rw = _resized_hw(h0, w0, s)
+        hw.append((rh, rw))
+        j.src[t], j.h0[t], j.w0[t], j.stride[t], j.rh[t], j.rw[t] = im.data_ptr(), h0, w0, int(im.stride(0)), rh, rw
+    mosaic, pads = d.get("mosaic", True), None
+    if mosaic:
+        rects = _tile_rects(hw, d["yc"], d["xc"], s)
+    else:
+        # letterbox(auto=False, scaleup=True) of an image whose longest side already is s (augmentations.py:85-115): r = 1, no second resize;
+        # the image sits at (left, top) = (round(dw - 0.1), round(dh - 0.1)) of an s x s canvas of 114s, the labels move by the FLOAT dw, dh
+        (rh, rw), = hw
+        dw, dh = (s - rw) / 2, (s - rh) / 2
+        left, top = int(round(dw - 0.1)), int(round(dh - 0.1))
+        rects, pads = [(left, top, left + rw, top + rh, 0, 0)], [(dw, dh)]
+        j.canvas = s
+    for t, (x1a, y1a, x2a, y2a, x1b, y1b) in enumerate(rects):
+        j.x1a[t], j.y1a[t], j.x2a[t], j.y2a[t], j.x1b[t], j.y1b[t] = x1a, y1a, x2a, y2a, x1b, y1b
+    M, width, height = _affine(d, s, mosaic)
+    A = _invert_affine(M)
+    for k in range(6):
+        j.A[k] = float(A.reshape(-1)[k])
+    return hw, rects, pads, M, width, height
+
+
+def _finish_job(j, d, use_hsv):
+    """HSV look-up tables (augmentations.py:76-79) and flips of one rendered job."""
+    x = np.arange(0, 256, dtype=np.float64)
+    r = np.asarray(d["hsv"], dtype=np.float64)
+    luts = (((x * r[0]) % 180).astype(np.uint8), np.clip(x * r[1], 0, 255).astype(np.uint8), np.clip(x * r[2], 0, 255).astype(np.uint8))
+    for c in range(3):
+        C.memmove(j.lut[c], luts[c].ctypes.data, 256)
+    j.hsv, j.flipud, j.fliplr = int(use_hsv), int(bool(d["flipud"])), int(bool(d["fliplr"]))
+
+
+def _render(jobs, B, s, dev, dtype, normalize):
+    """The y5_mosaic_batch launch over a filled job table -> (B, 3, s, s)."""
+    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev)
+    out = torch.empty((B, 3, s, s), dtype=dtype, device=dev)
+    code = {torch.uint8: _lib.Y5_U8, torch.float16: _lib.Y5_F16, torch.float32: _lib.Y5_F32}[dtype]
+    lib = _lib.lib()
+    _lib.check(lib.y5_mosaic_batch(C.c_void_p(table.data_ptr()), B, s, 114, C.c_void_p(out.data_ptr()), code, int(normalize and dtype != torch.uint8),
+                                   _lib.stream(dev)), lib)
+    return out
+
+
 def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normalize=False):
     """Render one training batch.  images: list of uint8 (h, w, 3) BGR tensors resident on the device (any sizes); labels: list of
     (k, 5) arrays [cls, xc, yc, w, h] normalised; draws: list (one per output image) of `draw_sample` dicts.
@@ -185,35 +241,8 @@ def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normaliz
     B = len(draws)
     labs = []
     use_hsv = bool(hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"])
-    x = np.arange(0, 256, dtype=np.float64)
     def fill(j, d):
-        """Geometry half of one job (tiles, rectangles, inverse affine map) -> the pixel boxes of its labels after random_perspective."""
-        hw = []
-        for t, i in enumerate(d["indices"]):
-            im = images[i]
-            if not (_lib.accepts(im) and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
-                raise ValueError("mosaic_batch: images must be uint8 (h, w, 3) device tensors with contiguous rows")
-            h0, w0 = int(im.shape[0]), int(im.shape[1])
-            rh, rw = _resized_hw(h0, w0, s)
-            hw.append((rh, rw))
-            j.src[t], j.h0[t], j.w0[t], j.stride[t], j.rh[t], j.rw[t] = im.data_ptr(), h0, w0, int(im.stride(0)), rh, rw
-        mosaic, pads = d.get("mosaic", True), None
-        if mosaic:
-            rects = _tile_rects(hw, d["yc"], d["xc"], s)
-        else:
-            # letterbox(auto=False, scaleup=True) of an image whose longest side already is s (augmentations.py:85-115): r = 1, no second resize;
-            # the image sits at (left, top) = (round(dw - 0.1), round(dh - 0.1)) of an s x s canvas of 114s, the labels move by the FLOAT dw, dh
-            (rh, rw), = hw
-            dw, dh = (s - rw) / 2, (s - rh) / 2
-            left, top = int(round(dw - 0.1)), int(round(dh - 0.1))
-            rects, pads = [(left, top, left + rw, top + rh, 0, 0)], [(dw, dh)]
-            j.canvas = s
-        for t, (x1a, y1a, x2a, y2a, x1b, y1b) in enumerate(rects):
-            j.x1a[t], j.y1a[t], j.x2a[t], j.y2a[t], j.x1b[t], j.y1b[t] = x1a, y1a, x2a, y2a, x1b, y1b
-        M, width, height = _affine(d, s, mosaic)
-        A = _invert_affine(M)
-        for k in range(6):
-            j.A[k] = float(A.reshape(-1)[k])
+        hw, rects, pads, M, width, height = _fill_job(j, images, d, s)
         return _labels(labels, d, hw, rects, M, width, height, s, pads), width, height
 
     partners = [d for d in draws if d.get("partner") is not None]
@@ -227,20 +256,11 @@ def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normaliz
             j.mix_job, j.mix_r = B + npart + 1, float(d["mix_r"])
             npart += 1
             t = np.concatenate((t, t2), 0)
-        r = np.asarray(d["hsv"], dtype=np.float64)
-        luts = (((x * r[0]) % 180).astype(np.uint8), np.clip(x * r[1], 0, 255).astype(np.uint8), np.clip(x * r[2], 0, 255).astype(np.uint8))
-        for c in range(3):
-            C.memmove(j.lut[c], luts[c].ctypes.data, 256)
-        j.hsv, j.flipud, j.fliplr = int(use_hsv), int(bool(d["flipud"])), int(bool(d["fliplr"]))
+        _finish_job(j, d, use_hsv)
         lb = _finish_labels(t, d, width, height)
         lb[:, 0] = b                                             # collate_fn (dataloaders.py:860-862)
         labs.append(lb)
-    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev)
-    out = torch.empty((B, 3, s, s), dtype=dtype, device=dev)
-    code = {torch.uint8: _lib.Y5_U8, torch.float16: _lib.Y5_F16, torch.float32: _lib.Y5_F32}[dtype]
-    lib = _lib.lib()
-    _lib.check(lib.y5_mosaic_batch(C.c_void_p(table.data_ptr()), B, s, 114, C.c_void_p(out.data_ptr()), code, int(normalize and dtype != torch.uint8),
-                                   _lib.stream(dev)), lib)
+    out = _render(jobs, B, s, dev, dtype, normalize)
     targets = torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
     return out, targets
 
@@ -283,3 +303,337 @@ class MosaicLoader:
             imgs, targets = mosaic_batch(self.images, self.labels, draws, self.s, self.hyp, self.dtype, normalize=True)
             yield imgs, targets, [self.paths[i] for i in ids], None
         self.epoch += 1
+
+
+# ---- segmentation datasets: utils/segment/dataloaders.py:130-301, utils/segment/augmentations.py:14-91 ---------------------------------
+def labels_from_segments(cls, segments):
+    """(k, 5) float32 [cls, xc, yc, w, h] from k polygons: the `segments2boxes` rule the reference applies when it reads a polygon label
+    file (utils/dataloaders.py:923; general.py `segments2boxes`: min / max of the polygon, then xyxy2xywh), so a dataset needs only polygons."""
+    boxes = []
+    for sgm in segments:
+        x, y = np.asarray(sgm).T
+        boxes.append([x.min(), y.min(), x.max(), y.max()])
+    b = np.array(boxes, dtype=np.float64).reshape(-1, 4)
+    out = np.empty((len(b), 5), dtype=np.float32)
+    out[:, 0] = np.asarray(cls, dtype=np.float32).reshape(-1)
+    out[:, 1], out[:, 2] = (b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2
+    out[:, 3], out[:, 4] = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+    return out
+
+
+def _perspective_draws(d, hyp, rng):
+    d["persp"] = (rng.uniform(-hyp["perspective"], hyp["perspective"]), rng.uniform(-hyp["perspective"], hyp["perspective"]))
+    d["angle"] = rng.uniform(-hyp["degrees"], hyp["degrees"])
+    d["scale"] = rng.uniform(1 - hyp["scale"], 1 + hyp["scale"])
+    d["shear"] = (rng.uniform(-hyp["shear"], hyp["shear"]), rng.uniform(-hyp["shear"], hyp["shear"]))
+    d["translate"] = (rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]), rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]))
+
+
+def draw_sample_seg(index, n_images, s, hyp, rng=random, np_rng=np.random):
+    """Random numbers of one sample in the order of the SEGMENTATION `__getitem__` (utils/segment/dataloaders.py), which is not `draw_sample`'s:
+    mosaic gate (:135); centre yc, xc (:239); three extra indices, NOT shuffled (:242); copy_paste draws nothing at p = 0 (:280);
+    random_perspective's eight (segment/augmentations.py:42-61); mixup gate (:141), partner = randint(0, n - 1) (:142), the partner mosaic's own
+    draws, np.random.beta (segment/augmentations.py:19); three HSV gains from numpy; flipud, fliplr gates (:212,219)."""
+    if hyp.get("copy_paste", 0.0):
+        raise NotImplementedError("SegMosaicLoader: copy_paste != 0 is not implemented")
+    if hyp["perspective"]:
+        raise NotImplementedError("SegMosaicLoader: perspective != 0 (cv2.warpPerspective) is not implemented")
+
+    def mosaic(i):
+        m = {"mosaic": True}
+        m["yc"], m["xc"] = (int(rng.uniform(-x, 2 * s + x)) for x in (-s // 2, -s // 2))
+        m["indices"] = [i, *rng.choices(range(n_images), k=3)]
+        _perspective_draws(m, hyp, rng)
+        return m
+
+    if rng.random() < hyp["mosaic"]:
+        d = mosaic(index)
+        if rng.random() < hyp["mixup"]:
+            d["partner"] = mosaic(rng.randint(0, n_images - 1))
+            d["mix_r"] = float(np_rng.beta(32.0, 32.0))
+    else:
+        d = {"mosaic": False, "indices": [index]}
+        _perspective_draws(d, hyp, rng)
+    d["hsv"] = np_rng.uniform(-1, 1, 3) * [hyp["hsv_h"], hyp["hsv_s"], hyp["hsv_v"]] + 1
+    d["flipud"] = rng.random() < hyp["flipud"]
+    d["fliplr"] = rng.random() < hyp["fliplr"]
+    return d
+
+
+_GRIDS = {}
+
+
+def _grid(k, n):
+    """np.linspace(0, k - 1, n) as np.interp sees it over xp = arange(k): interval index j, x - xp[j], and the exact hits of a knot."""
+    g = _GRIDS.get((k, n))
+    if g is None:
+        x = np.linspace(0, k - 1, n)
+        j = np.minimum(np.floor(x).astype(np.intp), max(k - 2, 0))
+        g = _GRIDS[(k, n)] = (j, np.minimum(j + 1, k - 1), x - j, x == j, x == j + 1)
+    return g
+
+
+def resample_segments(segs, n=1000):
+    """general.py:603-610 on a list of (k, 2) arrays -> (len, n, 2) float64.  np.interp over the integer knots xp = arange(k + 1) is
+    fp[j] + (fp[j + 1] - fp[j]) * (x - j) (its slope divides by xp[j + 1] - xp[j] = 1) with fp[j] returned where x hits a knot; polygons of
+    equal length share x, so they are resampled together (tests/test_emu_seg_data.py pins this against np.interp and the literal loop)."""
+    out = np.empty((len(segs), n, 2), dtype=np.float64)
+    by_len = {}
+    for i, sg in enumerate(segs):
+        by_len.setdefault(len(sg), []).append(i)
+    for k, ids in by_len.items():
+        fp = np.stack([segs[i] for i in ids]).astype(np.float64)
+        fp = np.concatenate((fp, fp[:, 0:1]), 1)
+        j, j1, dx, hit0, hit1 = _grid(k + 1, n)
+        a, b = fp.take(j, axis=1), fp.take(j1, axis=1)
+        v = (b - a) * dx[None, :, None] + a
+        out[ids] = np.where(hit0[None, :, None], a, np.where(hit1[None, :, None], b, v))
+    return out
+
+
+def _seg_labels(labels, segments, d, hw, rects, M, width, height, s, pads=None):
+    """Label half of one sample as utils/segment/augmentations.py:26-91 `random_perspective` computes it: tiles -> canvas pixels (xywhn2xyxy,
+    xyn2xy in float32), mosaic only: clip boxes and polygons to the canvas (:276-277), resample_segments(n = 1000), xy @ M.T, new box =
+    segment2box(xy, width, height) (NOT the warped corners), box_candidates(area_thr = 0.01).
+    -> ((k, 5) float32 [cls, x1, y1, x2, y2], (k, 1000, 2) float64 polygons) in output pixels."""
+    parts, segs, lens = [], [], []
+    for k, (i, (h, w), (x1a, y1a, _x2a, _y2a, x1b, y1b)) in enumerate(zip(d["indices"], hw, rects)):
+        lb = np.array(labels[i], dtype=np.float32).reshape(-1, 5).copy()
+        padw, padh = (x1a - x1b, y1a - y1b) if pads is None else pads[k]
+        if lb.size:
+            xy, half = lb[:, 1:3].copy(), lb[:, 3:5] / 2
+            lb[:, 1] = w * (xy[:, 0] - half[:, 0]) + padw
+            lb[:, 2] = h * (xy[:, 1] - half[:, 1]) + padh
+            lb[:, 3] = w * (xy[:, 0] + half[:, 0]) + padw
+            lb[:, 4] = h * (xy[:, 1] + half[:, 1]) + padh
+            if len(segments[i]) != len(lb):
+                raise ValueError(f"image {i}: {len(lb)} labels but {len(segments[i])} polygons")
+            sg = np.concatenate([np.asarray(g, dtype=np.float32).reshape(-1, 2) for g in segments[i]], 0)
+            y = np.copy(sg)                                            # xyn2xy (general.py:584-589) on all polygons of the tile at once
+            y[..., 0] = w * sg[..., 0] + padw
+            y[..., 1] = h * sg[..., 1] + padh
+            segs.append(y)
+            lens.extend(len(g) for g in segments[i])
+        parts.append(lb)
+    t = np.concatenate(parts, 0)
+    if d.get("mosaic", True):
+        np.clip(t[:, 1:], 0, 2 * s, out=t[:, 1:])
+        for x in segs:
+            np.clip(x, 0, 2 * s, out=x)
+    n = len(t)
+    if not n:
+        return t, np.zeros((0, 1000, 2))
+    pts = resample_segments(np.split(np.concatenate(segs, 0), np.cumsum(lens)[:-1]))
+    xy = np.ones((n, 1000, 3))
+    xy[:, :, :2] = pts
+    xy = (xy @ M.T)[:, :, :2]                                          # n products of the reference's own shape (1000, 3) @ (3, 3)
+    x, y = xy[:, :, 0], xy[:, :, 1]
+    ins = (x >= 0) & (y >= 0) & (x <= width) & (y <= height)            # segment2box (general.py:592-600)
+    any_in = ins.any(1)
+    new = np.stack((np.where(ins, x, np.inf).min(1), np.where(ins, y, np.inf).min(1), np.where(ins, x, -np.inf).max(1),
+                    np.where(ins, y, -np.inf).max(1)), 1)
+    new[~any_in] = 0.0
+    b1 = t[:, 1:5].T * d["scale"]
+    w1, h1 = b1[2] - b1[0], b1[3] - b1[1]
+    w2, h2 = new[:, 2] - new[:, 0], new[:, 3] - new[:, 1]
+    ar = np.maximum(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16))
+    keep = (w2 > 2) & (h2 > 2) & (w2 * h2 / (w1 * h1 + 1e-16) > 0.01) & (ar < 100)
+    t = t[keep]
+    t[:, 1:5] = new[keep]
+    return t, xy[keep]
+
+
+def polygon_masks(polys, inst_img, B, H, W, ratio, overlap, flips, device):
+    """ONE y5_polygon_masks call (csrc/seg_data.h) for the polygons of a batch.  polys: list of (k, 2) float pixel polygons in target order;
+    inst_img: their images, non-decreasing; flips: (B, 2) {up-down, left-right} or None.
+    -> (masks, order): overlap: (B, h, w) index planes (uint8 up to 255 instances per image, float32 beyond) and `order` (n,) on the HOST,
+    the per-image permutation (local indices) the target rows must follow -- the ONE device-to-host read; else (n, h, w) uint8, None."""
+    n = len(polys)
+    h, w = H // ratio, W // ratio
+    inst = np.asarray(inst_img, dtype=np.int32).reshape(-1)
+    if n and (inst.min() < 0 or inst.max() >= B or (np.diff(inst) < 0).any()):
+        raise ValueError("polygon_masks: inst_img must be non-decreasing image indices in [0, B)")
+    counts = np.bincount(inst, minlength=B) if n else np.zeros(B, np.int64)
+    f32 = bool(overlap) and n and int(counts.max()) > 255
+    dtype = torch.float32 if f32 else torch.uint8
+    masks = torch.empty((B if overlap else n, h, w), dtype=dtype, device=device)
+    lib = _lib.lib()
+    if n:
+        off = np.zeros(n + 1, dtype=np.int32)
+        np.cumsum([len(p) for p in polys], out=off[1:])
+        xy = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in polys], 0)
+        xy_d = torch.from_numpy(np.ascontiguousarray(xy)).to(device)
+        meta = torch.from_numpy(np.concatenate((off, inst))).to(device)
+        order = torch.empty(n, dtype=torch.int32, device=device)
+        area = torch.empty(n, dtype=torch.int64, device=device)
+        nb = int(lib.y5_polygon_masks_ws_bytes(n, H, W, ratio))
+        ws = _lib.workspace(nb, device)
+        ptrs = (xy_d.data_ptr(), meta.data_ptr(), meta.data_ptr() + 4 * (n + 1), order.data_ptr(), area.data_ptr(), ws.data_ptr())
+    else:
+        order, nb, ptrs = None, 0, (None,) * 6
+    fl = None if flips is None else torch.from_numpy(np.ascontiguousarray(np.asarray(flips, dtype=np.uint8).reshape(B, 2))).to(device)
+    if overlap or n:
+        _lib.check(lib.y5_polygon_masks(C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]), n, B, H, W, ratio, int(bool(overlap)),
+                                        C.c_void_p(fl.data_ptr() if fl is not None else None), C.c_void_p(masks.data_ptr()),
+                                        _lib.Y5_F32 if f32 else _lib.Y5_U8, C.c_void_p(ptrs[3]), C.c_void_p(ptrs[4]), C.c_void_p(ptrs[5]), nb,
+                                        _lib.stream(device)), lib)
+    if not overlap:
+        return masks, None
+    return masks, (order.cpu().numpy() if n else np.zeros(0, np.int32))
+
+
+def _reorder(labs, order):
+    """labels = labels[sorted_idx] (segment/dataloaders.py:189) for every image of the batch from the kernel's per-image permutations."""
+    out, o = [], 0
+    for lb in labs:
+        k = len(lb)
+        out.append(lb[order[o:o + k]] if k else lb)
+        o += k
+    return out
+
+
+def seg_mosaic_geometry(images, labels, segments, draws, s, hyp):
+    """Host half of `seg_mosaic_batch`: the filled y5_mosaic_batch job table, the (k, 6) targets of every image in LABEL order, and the warped
+    polygons (float64 output pixels) with their images -- the input of `polygon_masks`."""
+    B = len(draws)
+    use_hsv = bool(hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"])
+
+    def fill(j, d):
+        hw, rects, pads, M, width, height = _fill_job(j, images, d, s)
+        return _seg_labels(labels, segments, d, hw, rects, M, width, height, s, pads) + (width, height)
+
+    partners = [d for d in draws if d.get("partner") is not None]
+    jobs = (_lib.MosaicJob * (B + len(partners)))()
+    labs, polys, inst, npart = [], [], [], 0
+    for b, d in enumerate(draws):
+        j = jobs[b]
+        t, sg, width, height = fill(j, d)
+        if d.get("partner") is not None:                             # mixup (segment/augmentations.py:14-23): labels and segments concatenated
+            t2, sg2, _, _ = fill(jobs[B + npart], d["partner"])
+            j.mix_job, j.mix_r = B + npart + 1, float(d["mix_r"])
+            npart += 1
+            t, sg = np.concatenate((t, t2), 0), np.concatenate((sg, sg2), 0)
+        _finish_job(j, d, use_hsv)
+        lb = _finish_labels(t, d, width, height)
+        lb[:, 0] = b                                                 # collate_fn (segment/dataloaders.py:299-300)
+        labs.append(lb)
+        polys.extend(sg)
+        inst.extend([b] * len(sg))
+    return jobs, labs, polys, inst
+
+
+def seg_mosaic_batch(images, labels, segments, draws, s, hyp=None, dtype=torch.uint8, normalize=False, overlap=True, mask_ratio=4):
+    """One training batch of a segmentation dataset.  images / labels as `mosaic_batch`; segments[i]: the list of (k, 2) float arrays of
+    image i, normalised xy, one per label row; draws: `draw_sample_seg` dicts.  The image half is `mosaic_batch`'s launch over the same job
+    table.  Returns (imgs (B, 3, s, s), targets (nt, 6) float32 -- with overlap, the rows of every image in the mask kernel's area order --,
+    masks: overlap (B, s // mask_ratio, s // mask_ratio) index planes, else (nt, ...) 0 / 1 in target order)."""
+    hyp = HYP_AUG if hyp is None else hyp
+    dev = images[0].device
+    B = len(draws)
+    jobs, labs, polys, inst = seg_mosaic_geometry(images, labels, segments, draws, s, hyp)
+    out = _render(jobs, B, s, dev, dtype, normalize)
+    flips = [(bool(d["flipud"]), bool(d["fliplr"])) for d in draws]
+    masks, order = polygon_masks(polys, inst, B, s, s, mask_ratio, overlap, flips, dev)
+    if overlap:
+        labs = _reorder(labs, order)
+    targets = torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
+    return out, targets, masks
+
+
+class SegMosaicLoader(MosaicLoader):
+    """`MosaicLoader` for a segmentation dataset (utils/segment/dataloaders.py `LoadImagesAndLabelsAndMasks`, augment = True, rect = False):
+    yields (imgs, targets, paths, None, masks) as the reference's collate_fn does -- the batch `segment_loss.ComputeLoss` and
+    `train_loop.train` take.  labels may be None: they are then derived from the polygons (`labels_from_segments` needs `classes`)."""
+
+    def __init__(self, images, labels, segments, img_size=640, batch_size=16, hyp=None, dtype=torch.uint8, rank=-1, world_size=1, seed=0,
+                 paths=None, overlap=True, mask_ratio=4, classes=None):
+        if labels is None:
+            labels = [labels_from_segments(c, sg) for c, sg in zip(classes, segments)]
+        super().__init__(images, labels, img_size, batch_size, hyp, dtype, rank, world_size, seed, paths)
+        self.segments, self.overlap, self.mask_ratio = segments, overlap, mask_ratio
+
+    def __iter__(self):
+        g = random.Random(self.seed + self.epoch)
+        order = list(range(len(self.images)))
+        g.shuffle(order)
+        if self.rank != -1:
+            from .train_loop import pad_to_common
+
+            order = pad_to_common(order[self.rank::self.world], len(self.images), self.world)
+        for b0 in range(0, len(order), self.bs):
+            ids = order[b0:b0 + self.bs]
+            draws = [draw_sample_seg(i, len(self.images), self.s, self.hyp) for i in ids]
+            imgs, targets, masks = seg_mosaic_batch(self.images, self.labels, self.segments, draws, self.s, self.hyp, self.dtype, normalize=True,
+                                                    overlap=self.overlap, mask_ratio=self.mask_ratio)
+            yield imgs, targets, [self.paths[i] for i in ids], None, masks
+        self.epoch += 1
+
+
+def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, normalize=False, overlap=True, mask_ratio=1):
+    """The augment = False, rect = False branch of the segmentation `__getitem__` (utils/segment/dataloaders.py:144-199) + collate_fn for the
+    images `ids`: load_image, letterbox(auto=False, scaleup=False), labels and polygons to pixels with the float pad; the polygons are NOT
+    resampled (own lengths); no warp, no HSV, no flips.  The image half is a `y5_mosaic_batch` launch with one-tile jobs on an s x s canvas and
+    the identity map.  load_image's INTER_AREA for a down-scale without augmentation (dataloaders.py:784) is not restated: an image larger
+    than s is shrunk with INTER_LINEAR, as in the training branch.
+    Returns (imgs, targets, shapes, masks): shapes[i] = ((h0, w0), ((h / h0, w / w0), (dw, dh))) as :151."""
+    dev = images[0].device
+    B = len(ids)
+    jobs = (_lib.MosaicJob * B)()
+    ident = {"mosaic": False, "angle": 0.0, "scale": 1.0, "shear": (0.0, 0.0), "translate": (0.5, 0.5)}
+    labs, polys, inst, shapes = [], [], [], []
+    for b, i in enumerate(ids):
+        d = dict(ident, indices=[i])
+        j = jobs[b]
+        hw, rects, pads, _M, width, height = _fill_job(j, images, d, s)
+        (h, w), (dw, dh) = hw[0], pads[0]
+        h0, w0 = int(images[i].shape[0]), int(images[i].shape[1])
+        shapes.append(((h0, w0), ((h / h0, w / w0), (dw, dh))))
+        lb = np.array(labels[i], dtype=np.float32).reshape(-1, 5).copy()
+        sgs = []
+        if lb.size:
+            xy, half = lb[:, 1:3].copy(), lb[:, 3:5] / 2
+            lb[:, 1] = w * (xy[:, 0] - half[:, 0]) + dw
+            lb[:, 2] = h * (xy[:, 1] - half[:, 1]) + dh
+            lb[:, 3] = w * (xy[:, 0] + half[:, 0]) + dw
+            lb[:, 4] = h * (xy[:, 1] + half[:, 1]) + dh
+        for sg in segments[i]:
+            sg = np.asarray(sg, dtype=np.float32)
+            y = np.copy(sg)
+            y[..., 0] = w * sg[..., 0] + dw
+            y[..., 1] = h * sg[..., 1] + dh
+            sgs.append(y)
+        if len(sgs) != len(lb):
+            raise ValueError(f"image {i}: {len(lb)} labels but {len(sgs)} polygons")
+        res = _finish_labels(lb, {"flipud": False, "fliplr": False}, width, height)
+        res[:, 0] = b
+        labs.append(res)
+        polys.extend(sgs)
+        inst.extend([b] * len(sgs))
+    out = _render(jobs, B, s, dev, dtype, normalize)
+    masks, order = polygon_masks(polys, inst, B, s, s, mask_ratio, overlap, None, dev)
+    if overlap:
+        labs = _reorder(labs, order)
+    targets = torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
+    return out, targets, shapes, masks
+
+
+class SegValLoader:
+    """Validation loader of a segmentation dataset (augment = False, rect = False): yields the (imgs, targets, paths, shapes, masks)
+    five-tuple `segment_val.run` consumes, images in dataset order."""
+
+    def __init__(self, images, labels, segments, img_size=640, batch_size=16, dtype=torch.uint8, paths=None, overlap=True, mask_ratio=1, classes=None):
+        if labels is None:
+            labels = [labels_from_segments(c, sg) for c, sg in zip(classes, segments)]
+        self.images, self.labels, self.segments, self.s, self.bs = images, labels, segments, img_size, batch_size
+        self.dtype, self.overlap, self.mask_ratio = dtype, overlap, mask_ratio
+        self.paths = paths or [f"image{i}" for i in range(len(images))]
+
+    def __len__(self):
+        return (len(self.images) + self.bs - 1) // self.bs
+
+    def __iter__(self):
+        for b0 in range(0, len(self.images), self.bs):
+            ids = list(range(b0, min(b0 + self.bs, len(self.images))))
+            imgs, targets, shapes, masks = seg_letterbox_batch(self.images, self.labels, self.segments, ids, self.s, self.dtype, normalize=True,
+                                                               overlap=self.overlap, mask_ratio=self.mask_ratio)
+            yield imgs, targets, [self.paths[i] for i in ids], shapes, masks
