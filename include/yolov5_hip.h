@@ -231,7 +231,9 @@ long long y5_conv2d_wgrad_ws_bytes(const y5_conv_desc* d, int ld_dz);   /* < 0: 
 /* ---------------------------------------------------------------------------------------------------------
  * Train-mode Conv block pieces (models/common.py:82-88 `Conv.forward` = SiLU(BatchNorm2d(conv(x))) with BATCH
  * statistics; eps / momentum as set by initialize_weights, models/yolo.py:259).  z = raw conv output (y5_conv2d_fwd
- * with act = 0 and zero bias), NHWC slice, npix = B*OH*OW pixels, C channels (C*elemsize % 16 == 0).
+ * with act = 0 and zero bias), NHWC slice, npix = B*OH*OW pixels, C channels (C*elemsize % 16 == 0, at most 256 vectors of 16 bytes:
+ * C <= 2048 in fp16, <= 1024 in fp32).  Every pixel stride (ldz, ldy, ld_dy, ld_dz, ld; ldr when a residual is given) must be >= C and a
+ * multiple of 16 bytes: Y5_ERR_BAD_ARG otherwise.
  * y5_bn_silu_fwd: batch mean / biased variance per channel (deterministic two-level reduction) -> save_mean,
  *   save_invstd = 1/sqrt(var+eps); running stats updated like torch (unbiased variance, momentum); then
  *   y = [residual +] silu(gamma*(z-mean)*invstd + beta)   (residual = Bottleneck shortcut, common.py:181).

@@ -18,6 +18,12 @@ int check(int dt, long long npix, int C, const void* ws, size_t ws_bytes) {
   if (!ws || ws_bytes < y5_bn_workspace_bytes(C, npix) || ((uintptr_t)ws & 15)) return y5_fail(Y5_ERR_WORKSPACE, "bn: workspace too small or misaligned");
   return Y5_OK;
 }
+// every pixel stride goes straight into 16-byte vector loads / stores: it must cover the C channels and keep each pixel's slice 16-byte aligned
+int check_ld(int dt, int C, int ld, const char* what) {
+  const int vec = dt == Y5_F16 ? 8 : 4;
+  if (ld < C || ld % vec) return y5_fail(Y5_ERR_BAD_ARG, what);
+  return Y5_OK;
+}
 // (the reversed-walk statistics pass of round 5, Y5_BN_REV, measured neutral -- profiles/experiments/r05_bn_reverse_pass.log -- and lost its switch in round 6;
 // Y5BnParams.rev stays 0)
 template <int MODE>
@@ -44,6 +50,9 @@ extern "C" int y5_bn_silu_fwd(const void* z, int dt, long long npix, int C, int 
   hipStream_t st = static_cast<hipStream_t>(stream_);
   if (int rc = check(dt, npix, C, ws, ws_bytes)) return rc;
   if (!z || !gamma || !beta || !save_mean || !save_invstd || !y) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_fwd: null pointer");
+  if (check_ld(dt, C, ldz, "bn_silu_fwd: ldz must be >= C and a multiple of 16 bytes") || check_ld(dt, C, ldy, "bn_silu_fwd: ldy must be >= C and a multiple of 16 bytes") ||
+      (residual && check_ld(dt, C, ldr, "bn_silu_fwd: ldr must be >= C and a multiple of 16 bytes")))
+    return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.res = residual; p.out = y; p.gamma = gamma; p.beta = beta; p.mean = save_mean; p.invstd = save_invstd;
   p.running_mean = running_mean; p.running_var = running_var; p.partial = static_cast<float*>(ws);
@@ -67,6 +76,9 @@ extern "C" int y5_bn_silu_bwd(const void* dy, int ld_dy, const void* z, int ldz,
   hipStream_t st = static_cast<hipStream_t>(stream_);
   if (int rc = check(dt, npix, C, ws, ws_bytes)) return rc;
   if (!dy || !z || !gamma || !beta || !save_mean || !save_invstd || !dz || !dgamma || !dbeta) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_bwd: null pointer");
+  if (check_ld(dt, C, ld_dy, "bn_silu_bwd: ld_dy must be >= C and a multiple of 16 bytes") || check_ld(dt, C, ldz, "bn_silu_bwd: ldz must be >= C and a multiple of 16 bytes") ||
+      check_ld(dt, C, ld_dz, "bn_silu_bwd: ld_dz must be >= C and a multiple of 16 bytes"))
+    return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.dy = dy; p.out = dz; p.gamma = gamma; p.beta = beta;
   p.mean = const_cast<float*>(save_mean); p.invstd = const_cast<float*>(save_invstd);
@@ -86,6 +98,7 @@ extern "C" int y5_bn_stats(const void* z, int dt, long long npix, int C, int ldz
   hipStream_t st = static_cast<hipStream_t>(stream_);
   if (int rc = check(dt, npix, C, ws, ws_bytes)) return rc;
   if (!z || !sums) return y5_fail(Y5_ERR_BAD_ARG, "bn_stats: null pointer");
+  if (check_ld(dt, C, ldz, "bn_stats: ldz must be >= C and a multiple of 16 bytes")) return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.partial = static_cast<float*>(ws); p.sums = sums; p.npix = npix; p.C = C; p.ldz = ldz; p.nblk = nblk_for(npix);
   reduce<0>(p, dt, st);
@@ -101,6 +114,9 @@ extern "C" int y5_bn_silu_fwd_from_sums(const void* z, int dt, long long npix, i
   const int vec = dt == Y5_F16 ? 8 : 4;
   if (npix < 1 || count_total < npix || C < vec || C % vec || C / vec > 256) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_fwd_from_sums: bad npix / count / C");
   if (!z || !gamma || !beta || !save_mean || !save_invstd || !sums || !y) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_fwd_from_sums: null pointer");
+  if (check_ld(dt, C, ldz, "bn_silu_fwd_from_sums: ldz must be >= C and a multiple of 16 bytes") || check_ld(dt, C, ldy, "bn_silu_fwd_from_sums: ldy must be >= C and a multiple of 16 bytes") ||
+      (residual && check_ld(dt, C, ldr, "bn_silu_fwd_from_sums: ldr must be >= C and a multiple of 16 bytes")))
+    return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.res = residual; p.out = y; p.gamma = gamma; p.beta = beta; p.mean = save_mean; p.invstd = save_invstd;
   p.running_mean = running_mean; p.running_var = running_var; p.sums = const_cast<double*>(sums); p.count = count_total;
@@ -127,6 +143,9 @@ extern "C" int y5_bn_silu_fwd_from_partials(const void* z, int dt, long long npi
   const int vec = dt == Y5_F16 ? 8 : 4;
   if (npix < 1 || rows < 1 || C < vec || C % vec || C / vec > 256) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_fwd_from_partials: bad npix / rows / C");
   if (!z || !gamma || !beta || !save_mean || !save_invstd || !partial || !y) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_fwd_from_partials: null pointer");
+  if (check_ld(dt, C, ldz, "bn_silu_fwd_from_partials: ldz must be >= C and a multiple of 16 bytes") || check_ld(dt, C, ldy, "bn_silu_fwd_from_partials: ldy must be >= C and a multiple of 16 bytes") ||
+      (residual && check_ld(dt, C, ldr, "bn_silu_fwd_from_partials: ldr must be >= C and a multiple of 16 bytes")))
+    return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.res = residual; p.out = y; p.gamma = gamma; p.beta = beta; p.mean = save_mean; p.invstd = save_invstd;
   p.running_mean = running_mean; p.running_var = running_var; p.partial = const_cast<float*>(partial);
@@ -148,6 +167,8 @@ extern "C" int y5_bn_bwd_stats(const void* dy, int ld_dy, const void* z, int ldz
   hipStream_t st = static_cast<hipStream_t>(stream_);
   if (int rc = check(dt, npix, C, ws, ws_bytes)) return rc;
   if (!dy || !z || !gamma || !beta || !save_mean || !save_invstd || !dgamma || !dbeta) return y5_fail(Y5_ERR_BAD_ARG, "bn_bwd_stats: null pointer");
+  if (check_ld(dt, C, ld_dy, "bn_bwd_stats: ld_dy must be >= C and a multiple of 16 bytes") || check_ld(dt, C, ldz, "bn_bwd_stats: ldz must be >= C and a multiple of 16 bytes"))
+    return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.dy = dy; p.gamma = gamma; p.beta = beta; p.mean = const_cast<float*>(save_mean); p.invstd = const_cast<float*>(save_invstd);
   p.partial = static_cast<float*>(ws); p.dgamma = dgamma; p.dbeta = dbeta;
@@ -165,6 +186,9 @@ extern "C" int y5_bn_silu_bwd_from_sums(const void* dy, int ld_dy, const void* z
   const int vec = dt == Y5_F16 ? 8 : 4;
   if (npix < 1 || count_total < npix || C < vec || C % vec || C / vec > 256) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_bwd_from_sums: bad npix / count / C");
   if (!dy || !z || !gamma || !beta || !save_mean || !save_invstd || !sum_dgamma || !sum_dbeta || !dz) return y5_fail(Y5_ERR_BAD_ARG, "bn_silu_bwd_from_sums: null pointer");
+  if (check_ld(dt, C, ld_dy, "bn_silu_bwd_from_sums: ld_dy must be >= C and a multiple of 16 bytes") || check_ld(dt, C, ldz, "bn_silu_bwd_from_sums: ldz must be >= C and a multiple of 16 bytes") ||
+      check_ld(dt, C, ld_dz, "bn_silu_bwd_from_sums: ld_dz must be >= C and a multiple of 16 bytes"))
+    return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.z = z; p.dy = dy; p.out = dz; p.gamma = gamma; p.beta = beta; p.mean = const_cast<float*>(save_mean); p.invstd = const_cast<float*>(save_invstd);
   p.dgamma = const_cast<float*>(sum_dgamma); p.dbeta = const_cast<float*>(sum_dbeta); p.count = count_total;
@@ -179,6 +203,7 @@ extern "C" int y5_channel_sum(const void* x, int dt, long long npix, int C, int 
   hipStream_t st = static_cast<hipStream_t>(stream_);
   if (int rc = check(dt, npix, C, ws, ws_bytes)) return rc;
   if (!x || !out) return y5_fail(Y5_ERR_BAD_ARG, "channel_sum: null pointer");
+  if (check_ld(dt, C, ld, "channel_sum: ld must be >= C and a multiple of 16 bytes")) return Y5_ERR_BAD_ARG;
   Y5BnParams p{};
   p.dy = x; p.partial = static_cast<float*>(ws); p.dbeta = out; p.dgamma = nullptr;
   p.npix = npix; p.C = C; p.ldy = ld; p.nblk = nblk_for(npix);

@@ -9,6 +9,11 @@
 //   y5_bn_finish_kernel           partials -> mean / invstd (+ running stats update)   or   -> dgamma / dbeta
 //   y5_bn_silu_apply_kernel       y = [res +] silu(gamma * (z - mean) * invstd + beta)
 //   y5_bn_silu_bwd_apply_kernel   dz = gamma * invstd * (dv - dbeta/N - zhat * dgamma/N)
+//
+// Conditioning: the variance is the single-pass E[z^2] - mean^2 from fp32 partial sums, so y and dz keep their tolerances (fp32: rtol 1e-4 / atol 1e-5,
+// fp16: 5e-3 / 5e-3) up to |mean| / sigma = 16 and leave them beyond -- measured on the MI355X against float64 at |mean| / sigma = 64: fp32 2.6x (y) / 4.1x (dz)
+// its tolerance at 1 600 pixels, fp16 still inside; at 256: fp32 60x / 80x, fp16 2.9x / 2.3x (tests/test_gpu_train_glue.py).
+// One pixel per channel is exact by rule: variance 0, invstd = 1 / sqrt(eps).
 #pragma once
 #include "y5_common.h"
 
@@ -161,7 +166,7 @@ void y5_bn_finish_kernel(const Y5BnParams p) {
     const double n = (double)p.npix;
     const double mean = s0 / n;
     double var = s1 / n - mean * mean;
-    if (var < 0.0) var = 0.0;
+    if (var < 0.0 || n <= 1.0) var = 0.0;   // one pixel: the variance IS 0 (the fp32 square in s1 is rounded, the fp64 square of the mean is not)
     p.mean[c] = (float)mean;
     p.invstd[c] = (float)(1.0 / sqrt(var + (double)p.eps));
     if (p.running_mean) p.running_mean[c] = (1.0f - p.momentum) * p.running_mean[c] + p.momentum * (float)mean;
@@ -181,7 +186,7 @@ void y5_bn_from_sums_kernel(const Y5BnParams p) {
   const double n = (double)p.count;
   const double mean = p.sums[c] / n;
   double var = p.sums[p.C + c] / n - mean * mean;
-  if (var < 0.0) var = 0.0;
+  if (var < 0.0 || n <= 1.0) var = 0.0;   // (as y5_bn_finish_kernel)
   p.mean[c] = (float)mean;
   p.invstd[c] = (float)(1.0 / sqrt(var + (double)p.eps));
   if (p.running_mean) p.running_mean[c] = (1.0f - p.momentum) * p.running_mean[c] + p.momentum * (float)mean;
