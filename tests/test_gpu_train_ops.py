@@ -245,7 +245,9 @@ def test_conv_dgrad(case, dev):
     ref = x.grad.permute(0, 2, 3, 1)
     if acc:
         ref = ref + init.float()
-    torch.testing.assert_close(dxd[..., :C1].float().cpu(), ref, rtol=2e-2, atol=3e-2)
+    # two fp16 roundings at most (the convolution, then the sum with the residual: 2 * 2^-11 |ref|) + the fp32 accumulation, measured at a few 1e-8 of
+    # the sum of absolute products (tests/conv_grad_ref.py): ten times tighter than the 2e-2 / 3e-2 this test started with
+    torch.testing.assert_close(dxd[..., :C1].float().cpu(), ref, rtol=2e-3, atol=2e-3)
     assert torch.all(dxd[..., C1:] == 0)
 
 

@@ -115,6 +115,8 @@ int launch_cfg(const Y5ConvParams& p0, int max_blocks, hipStream_t stream) {
     G = (long long)g_num_cu * occ;
   }
   if constexpr (SK) {
+    // (refused before the workspace is looked at: a placed launch has no stream-K build with or without one)
+    if (p.o_mul_h) return y5_fail(Y5_ERR_UNSUPPORTED, "conv: stream-K with output placement is not built");
     // every resident workgroup gets an equal share of the tiles * nk chunk-units (at least two chunks each)
     const long long U = ntiles * p.nk;
     if (G > U / 2) G = U / 2 > 0 ? U / 2 : 1;
@@ -126,7 +128,6 @@ int launch_cfg(const Y5ConvParams& p0, int max_blocks, hipStream_t stream) {
     if (!w.ws || w.bytes < need) return y5_fail(Y5_ERR_WORKSPACE, "conv: stream-K configuration needs y5_conv_set_sk_workspace()");
     p.sk_flags = static_cast<unsigned*>(w.ws);
     p.sk_ws = reinterpret_cast<float*>(static_cast<char*>(w.ws) + kSkFlagBytes);
-    if (p.o_mul_h) return y5_fail(Y5_ERR_UNSUPPORTED, "conv: stream-K with output placement is not built");
   } else {
     if (G > ntiles) G = ntiles;
     if (G >= 8) G &= ~7LL;  // y5_xcd_remap of the virtual block id needs G % 8 == 0 when blocks own several tiles
@@ -530,7 +531,7 @@ static int conv2d_fwd_impl(const y5_conv_desc* d, const void* x, const void* w_p
   const bool k3 = (fam >= kK3_0 && fam < kBig0) || k3w;
   const int k3i = k3w ? 5 + fam - kK3W_0 : fam - kK3_0;
   const int bk = up2 ? kUpCfgs[cfg - kUp0].rb / es : (pw || k3 || h3) ? 8 : (sk ? kSkCfgs[fam - kSk0].rb : big ? kBigCfgs[fam - kBig0].rb : kCfgs[fam >= kRing0 ? kRingBase[fam - kRing0] : fam].rb) / es;
-  if (fam >= kRing0 && d->dtype != Y5_F16) return y5_fail(Y5_ERR_UNSUPPORTED, "conv: ring configurations are fp16 only");
+  if (fam >= kRing0 && d->dtype != Y5_F16) return y5_fail(Y5_ERR_UNSUPPORTED, "conv: configurations 22 and above are fp16 only");
   if (d->C1 % epp || d->ldx % epp) return y5_fail(Y5_ERR_BAD_ARG, "conv: C1 and ldx must be multiples of 16 bytes");
   if (d->C2 % epp || (y && d->ldy % epp) || (residual && d->ldr % epp) || (y_up2 && d->ld2 % epp))
     return y5_fail(Y5_ERR_BAD_ARG, "conv: C2/ldy/ldr/ld2 must be multiples of 16 bytes");
