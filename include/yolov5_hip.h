@@ -694,6 +694,33 @@ int y5_mt_sgd_step(const y5_mt_tensor* table_dev, int ntensors, long long max_nu
                    int nesterov, float inv_scale, const float* stats_dev, float ema_decay, void* stream);
 int y5_mt_lerp(const y5_mt_tensor* table_dev, int ntensors, long long max_numel, float decay, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * AutoAnchor (utils/autoanchor.py) -- csrc/autoanchor.h.  `wh` / `obs` are (n, 2) fp32 device rows; every reduction is deterministic
+ * (fixed-order partials, no floating-point atomics): two runs on the same input give the same bits.
+ *   anchor_metric : check_anchors.metric (:36-43) as exact integers.  x = min over the 2 dims of min(r, 1 / r), r = wh / k (IEEE fp32
+ *                   divisions, as torch); counts[0] = labels with max-over-anchors x > thr_inv (bpr * n), counts[1] = (label, anchor)
+ *                   pairs with x > thr_inv (aat * n).  k (na, 2) fp32, thr_inv = float32(1 / thr), counts = 2 int64 on the device.
+ *   anchor_evolve : the mutate-and-keep-if-fitter chain of kmean_anchors (:148-160) on the stream, no host synchronisation.  k (na, 2) and
+ *                   f (1) are fp64 DEVICE values updated in place; init_f != 0 first sets f = anchor_fitness(k) (:148).  v (gen, na, 2) fp64:
+ *                   the mutation factors of all generations, drawn up front.  Per generation kg = max(k * v_g, 2.0) in fp64, rounded to
+ *                   fp32 for the metric, fg = mean(best * (best > thr_inv)) with the sum in fp64, `if fg > f: f, k = fg, kg`;
+ *                   accepted[g] (uint8) records the decision.  na <= 40.
+ *   anchor_kmeans : scipy.cluster.vq.kmeans(obs, k, iter=R) as :139 calls it, all R restarts advancing together, in fp64: guess (R, k, 2)
+ *                   fp32 = the observations each restart starts from; per iteration every chain assigns each observation to its nearest
+ *                   live centroid (lowest index on ties), records the mean Euclidean distance, moves the centroids to their members'
+ *                   means, drops centroids without members for good (alive = 0), and freezes once the mean distance moved by <= 1e-5.
+ *                   init != 0 loads the guess; `steps` iterations are queued per call (frozen chains do nothing); *done (device int)
+ *                   is 1 once every chain is frozen -- the caller polls it between calls.  Outputs (device): book (R, k, 2) fp64,
+ *                   alive (R, k) uint8, last_dist (R) fp64, iters (R) int32.  Y5_ERR_UNSUPPORTED when R * k does not fit the LDS sums.
+ * --------------------------------------------------------------------------------------------------------- */
+int y5_anchor_metric(const float* wh, long long n, const float* k, int na, float thr_inv, long long* counts, void* stream);
+size_t y5_anchor_evolve_ws_bytes(long long n);
+int y5_anchor_evolve(const float* wh, long long n, int na, double* k, double* f, int init_f, const double* v, int gen, float thr_inv,
+                     unsigned char* accepted, void* workspace, size_t workspace_bytes, void* stream);
+size_t y5_anchor_kmeans_ws_bytes(long long n, int R, int k);
+int y5_anchor_kmeans(const float* obs, long long n, const float* guess, int R, int k, int init, int steps, double* book,
+                     unsigned char* alive, double* last_dist, int* iters, int* done, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

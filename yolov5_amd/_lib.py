@@ -203,6 +203,13 @@ EXPORTS = {
                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_scale_boxes_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "y5_anchor_metric": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "y5_anchor_evolve_ws_bytes": (C.c_size_t, [C.c_longlong]),
+    "y5_anchor_evolve": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "y5_anchor_kmeans_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "y5_anchor_kmeans": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_plan_create": (C.c_void_p, []),
     "y5_plan_destroy": (None, [C.c_void_p]),
     "y5_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

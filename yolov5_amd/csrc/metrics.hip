@@ -159,6 +159,8 @@ void y5_scale_boxes_kernel(float* __restrict__ det, int ld, int max_det, const i
   r[0] = x1; r[1] = y1; r[2] = x2; r[3] = y2;
 }
 
+#include "autoanchor.h"   // AutoAnchor: anchor metric, evolution chain, k-means (utils/autoanchor.py)
+
 extern "C" int y5_scale_boxes_batch(float* det, int ld_det, int max_det, const int* det_count, int bs, const float* scale, int do_round,
                                     void* stream_) {
   if (!det || !scale) return y5_fail(Y5_ERR_BAD_ARG, "scale_boxes_batch: null pointer");

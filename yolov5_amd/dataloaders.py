@@ -286,6 +286,12 @@ class MosaicLoader:
     def sampler(self):
         return self
 
+    @property
+    def shapes(self):
+        """(n_images, 2) float64 (w, h) of the source images, like the reference dataset's `.shapes` (utils/dataloaders.py:558): with `.labels`
+        this is all autoanchor.check_anchors / kmean_anchors read, so the loader can be passed to them as the dataset."""
+        return np.array([[int(im.shape[1]), int(im.shape[0])] for im in self.images], dtype=np.float64)
+
     def __len__(self):
         return (self.n_local + self.bs - 1) // self.bs
 

@@ -105,14 +105,19 @@ def host_amp_step(optimizer, parameters, scaler, max_norm=10.0):
 
 def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_lr=False, amp=True, ema=True, world_size=1, rank=-1,
           optimizer_name="SGD", max_norm=10.0, start_epoch=0, on_batch_end=None, nbs=64, val_loader=None, noval=False, sync_bn=False,
-          overlap=True):
+          overlap=True, autoanchor=None, imgsz=None):
     """Runs `epochs` epochs over `loader` (iterable of (imgs uint8|float BCHW, targets (nt, 6), *rest), re-iterable, len() = batches
     per epoch).  Returns dict(model, ema, optimizer, scheduler, scaler, mloss per epoch, losses per iteration, lr per epoch).
     rank / world_size as train.py's RANK / WORLD_SIZE (-1 / 1: single process; otherwise torch.distributed is initialised and the
     model is wrapped by smart_DDP).  val_loader: validated once per epoch on rank -1 / 0 with the EMA model (train.py:440-455 -> val_loop.run;
     noval: only after the final epoch); sync_bn: train.py:269-271 (`--sync-bn` under DDP: BatchNorm statistics over the global batch); `results` per validated epoch = (P, R, mAP@.5, mAP@.5:.95, val box / obj / cls loss), `fitness` beside it.
     Segment model (segment/train.py): the segmentation ComputeLoss(model, overlap=overlap) (:160,324), batch[4] = masks (:355,381), loss items
-    (lbox, lseg, lobj, lcls); mask-mAP validation is not implemented (val_loader raises)."""
+    (lbox, lseg, lobj, lcls); mask-mAP validation is not implemented (val_loader raises).
+    autoanchor: a dataset (.shapes, .labels -- a MosaicLoader / SegMosaicLoader qualifies) to fit the anchors to before the first step
+    (train.py:314-315 `check_anchors(dataset, model, thr=hyp['anchor_t'], imgsz)`: rank -1 / 0 of a run with start_epoch == 0, then a broadcast
+    from rank 0); imgsz defaults to the loader's `s`, else 640.  NOTE the default differs from train.py's: there AutoAnchor runs unless
+    `--noautoanchor` is given, here it runs only when asked for -- with None nothing changes and no RNG is consumed.  The result
+    (bpr, aat, replaced) is returned under "autoanchor"."""
     from .yolo import Segment
 
     seg = isinstance(de_parallel(model).model[-1], Segment)
@@ -126,6 +131,15 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
     total_batch = batch_size * world_size if rank != -1 else batch_size  # train.py works with the TOTAL batch size here
     accumulate = max(round(nbs / total_batch), 1)                                  # :235
     hyp["weight_decay"] *= total_batch * accumulate / nbs                           # :236
+    aa_result = None
+    if autoanchor is not None and start_epoch == 0:                                 # :314-315, before the optimizer and the DDP wrap
+        det = de_parallel(model).model[-1]
+        if rank in (-1, 0):
+            from .autoanchor import check_anchors
+
+            aa_result = check_anchors(autoanchor, model, thr=hyp["anchor_t"], imgsz=imgsz or getattr(autoanchor, "s", None) or 640)
+        if rank != -1 and world_size > 1:
+            dist.broadcast(det.anchors, 0)
     optimizer = smart_optimizer(model, optimizer_name, hyp["lr0"], hyp["momentum"], hyp["weight_decay"])  # :237
     lf = lr_lambda(epochs, hyp["lrf"], cos_lr)
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda=lf)          # :248
@@ -211,7 +225,8 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
     ni_ = 4 if seg else 3
     hist["losses"] = torch.stack(hist["losses"]).float().cpu() if hist["losses"] else torch.zeros(0, ni_)
     hist["mloss"] = torch.stack(hist["mloss"]).float().cpu() if hist["mloss"] else torch.zeros(0, ni_)
-    return dict(model=de_parallel(ddp), ema=ema_obj, optimizer=optimizer, scheduler=scheduler, scaler=scaler, best_fitness=best_fitness, **hist)
+    return dict(model=de_parallel(ddp), ema=ema_obj, optimizer=optimizer, scheduler=scheduler, scaler=scaler, best_fitness=best_fitness, autoanchor=aa_result,
+                **hist)
 
 
 def pad_to_common(idx, n, world_size):
