@@ -586,6 +586,29 @@ def test_plan_k3pw_fused_equals_unfused_on_gpu(dev, monkeypatch):
     assert float((u - v).abs().max()) <= 4e-3 * max(1.0, float(u.abs().max()))
 
 
+def test_plan_front_fused_equals_unfused_on_gpu(dev, monkeypatch):
+    """yolov5s 2 x 3 x 320 x 320 fp16: the plan with 0.Conv + 1.Conv + 2.C3.cv1+cv2 as ONE launch (Y5_FUSED_FRONT=1: taken whenever the library accepts the
+    shape, not only when the timing race at plan build picks it) against the plan with the stem and conv+pw launches (same fp16 intermediates, LDS and
+    registers instead of HBM)."""
+    from yolov5_amd.yolo import DetectionModel
+
+    cfg = yo.model_cfg("yolov5s")
+    sd = yo.det_state_dict(cfg, 0, fused=False)
+    x = torch.from_numpy(detgen.uniform((2, 3, 320, 320), 0.0, 1.0, name="img", seed=0)).half().to(dev)
+    monkeypatch.setenv("Y5_FUSED_K3PW", "1")
+    outs = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv("Y5_FUSED_FRONT", mode)
+        m = DetectionModel("yolov5s.yaml")
+        m.load_state_dict(sd)
+        m = m.eval().fuse().half().to(dev)
+        outs[mode] = m(x)[0].float().cpu()
+        eng = next(iter(m._engines.values()))
+        assert any(n.startswith("front:") for n in eng.op_names) == (mode == "1"), eng.op_names
+    u, v = outs["0"], outs["1"]
+    assert float((u - v).abs().max()) <= 4e-3 * max(1.0, float(u.abs().max()))
+
+
 def test_nms_objectness_hint_from_the_engine(dev):
     """The engine writes an objectness plane beside z (y5_plan_set_obj_hint) and hangs it on the tensor; non_max_suppression(z) then filters through
     the plane.  Same detections, bit for bit, as on a copy of z (no plane: the filter reads the rows), for the conv + decode levels and the fused P3 head;

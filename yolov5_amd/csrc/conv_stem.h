@@ -82,7 +82,10 @@ void y5_conv_stem_kernel(const Y5StemParams p) {
   const int G = gridDim.x, bid = blockIdx.x;
   const int nbt = (p.nwt + 3) >> 2;
   const int nmine = (nbt - bid + G - 1) / G;
-  auto tile_id = [&](int j) { return y5_xcd_remap(bid + j * G, nbt) * 4 + wave; };
+  // (fewer than eight workgroups walk the tiles in plain order: the remap puts the LAST tile, the only one that may be partial, at linear index
+  // 8 * (nbt / 8) - 1 when nbt % 8 != 0 -- the last step of its owner only for G >= 8; at G = 3, nbt = 39 it was step 10 of 13, and the waves
+  // past nwt went on to read and write three wave tiles behind the batch)
+  auto tile_id = [&](int j) { return (G >= 8 ? y5_xcd_remap(bid + j * G, nbt) : bid + j * G) * 4 + wave; };
   int nw = nmine;
   if (nw > 0 && tile_id(nw - 1) >= p.nwt) --nw;
 
