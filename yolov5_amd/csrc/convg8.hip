@@ -3,9 +3,11 @@
 
 #include "../../include/yolov5_hip.h"
 #include "conv_g8.h"
+#include "conv_cfgs.h"
 #include "y5_host.h"
 
-// idx 0 (id 95): 256 pixels x 256 channels; idx 1 (id 96): 256 pixels x 128 channels; K tile 64, mfma_f32_32x32x16_f16
+// kG8Cfgs row 0 (id 95): 256 pixels x 256 channels; row 1 (id 96): 256 pixels x 128 channels; K tile 64, mfma_f32_32x32x16_f16
+static_assert(Y5G8Geom::BN == kG8Cfgs[0].bn && Y5G8nGeom::BN == kG8Cfgs[1].bn, "kG8Cfgs rows out of step with the kernels' geometry");
 template <typename Gm, typename K>
 static int launch_g8(K kern, const Y5ConvParams& p0, int max_blocks, hipStream_t stream, bool seq_kernel = false) {
   Y5ConvParams p = p0;
@@ -37,13 +39,13 @@ static int launch_g8(K kern, const Y5ConvParams& p0, int max_blocks, hipStream_t
   return y5_check_launch("y5_conv2d_fwd(g8)");
 }
 
-int y5_launch_g8_by_cfg(const Y5ConvParams& p, int idx, int max_blocks, hipStream_t stream) {
+int y5_launch_g8_row(const Y5ConvParams& p, int row, int max_blocks, hipStream_t stream) {
   const bool up = p.up_c > 0;   // virtual Upsample + Concat loader (1x1 s1 layers; validated by the caller)
   const bool gen = (p.C1 % 64) != 0;   // general-C1 loader (conv_g8.h GEN): a K tile may span two taps
   if (p.C1 % 8 || p.C1 < 64 || p.KH * p.KW > (gen ? 31 : 32) || p.Kpad % 64 || p.Kpad < p.K || p.Npad > Y5G8Geom::MAXN || (gen && up))
     return y5_fail(Y5_ERR_UNSUPPORTED, "conv: the 8-phase configurations need C1 % 8 == 0, C1 >= 64 (C1 % 64 == 0 with up_c > 0), Kpad % 64 == 0, KH * KW <= 32 (31 unless C1 % 64 == 0) and Npad <= 2048");
   const bool seq = !up && !gen && p.KH == 3 && p.KW == 3 && p.SH == 2 && p.SW == 2;   // class-ordered taps (launch_g8 fills Y5ConvParams::tap_seq)
-  switch (idx) {
+  switch (row) {
     case 0:
       if (gen) return launch_g8<Y5G8Geom>(y5_conv_g8_kernel<false, false, true>, p, max_blocks, stream);
       if (seq) return launch_g8<Y5G8Geom>(y5_conv_g8_kernel<false, true>, p, max_blocks, stream, true);

@@ -1,42 +1,13 @@
-// Host-side launcher of the halo-resident 3x3 convolution (conv_h3.h); reached through y5_conv2d_fwd (conv.hip), configuration ids 61..
+// Host-side launcher of the halo-resident 3x3 convolution (conv_h3.h); reached through y5_conv2d_fwd (conv.hip), configuration ids of kH3Cfgs / kPwkCfgs (conv_cfgs.h)
 #include <hip/hip_runtime.h>
 
 #include "../../include/yolov5_hip.h"
 #include "conv_h3.h"
 #include "conv_pwk.h"
+#include "conv_cfgs.h"
 #include "y5_host.h"
 
 namespace {
-
-// ---- halo-resident 3x3 configurations (conv_h3.h): ids kH3_0 + index ------------------------------------------------------------
-struct H3Cfg { int wm, wn, tm, tn, hpmax; };
-constexpr int kNumH3 = 20;
-constexpr H3Cfg kH3Cfgs[kNumH3] = {
-    {2, 2, 5, 2, 496},  // 61: 320 pixels x 128 channels (8 x 40, 4 x 80, 16 x 20 output tiles)
-    {2, 2, 5, 1, 496},  // 62: 320 x  64
-    {2, 2, 7, 2, 512},  // 63: 448 x 128 (10 x 40: four tiles per 40 x 40 image; 20 x 20 whole images)
-    {2, 2, 4, 2, 400},  // 64: 256 x 128 (5 x 40, 10 x 20)
-    {2, 2, 7, 1, 512},  // 65: 448 x  64
-    {2, 2, 4, 1, 400},  // 66: 256 x  64
-    // eight waves (two per SIMD: one wave's LDS latency and DMA issue hide behind the other's MFMAs)
-    {2, 4, 5, 1, 496},  // 67: 320 x 128
-    {2, 4, 7, 1, 512},  // 68: 448 x 128
-    {2, 4, 4, 1, 400},  // 69: 256 x 128
-    {4, 2, 2, 2, 400},  // 70: 256 x 128, waves 4 x 2
-    // 128 x 128 (four waves) / 128 x 64 (eight waves) register tiles per wave: 2 MFMAs per fragment read
-    {4, 1, 4, 4, 512},  // 71: 512 x 128
-    {4, 2, 4, 2, 512},  // 72: 512 x 128, eight waves
-    // 4-stage filter ring: two workgroups per CU (independent barriers: one's LDS-DMA issue and epilogue overlap the other's MFMAs)
-    {2, 2, 4, 2, 320},  // 73: 256 x 128 (5 x 40, 10 x 20)
-    {2, 2, 4, 1, 320},  // 74: 256 x  64
-    {2, 2, 3, 2, 320},  // 75: 192 x 128
-    {4, 2, 2, 2, 320},  // 76: 256 x 128, eight waves, two workgroups per CU
-    {4, 2, 2, 1, 320},  // 77: 256 x  64, eight waves, two workgroups per CU
-    // round 5 (ids 90..92): small pixel tiles for the STRIDE-2 layers, whose halo is ~4.6x the output tile (4 x 16 outputs <- 9 x 33 inputs)
-    {2, 2, 1, 2, 320},  // 90:  64 x 128, four waves, 4-stage ring: two workgroups per CU
-    {4, 2, 1, 2, 592},  // 91: 128 x 128, eight waves, 4-stage ring (8 x 16 outputs <- 17 x 33 inputs)
-    {2, 2, 2, 2, 592},  // 92: 128 x 128, four waves, 4-stage ring
-};
 
 // spatial tile for an H x W output: TW = ceil(W / d), TH as tall as the pixel budget and the LDS halo allow, then evened out over the
 // image height; the candidate that needs the fewest rounds of `slots` concurrent workgroups wins, ties go to the smaller staged halo
@@ -73,13 +44,7 @@ int launch_h3(const Y5ConvParams& p0, int max_blocks, hipStream_t stream) {
   Y5ConvParams p = p0;
   if (p.Npad > Gm::BIAS_MAX) return y5_fail(Y5_ERR_UNSUPPORTED, "conv: halo 3x3 configurations stage at most 1024 output channels of bias");
   p.tilesN = (p.Npad + Gm::BN - 1) / Gm::BN;
-  long long G = max_blocks;
-  if (G <= 0) {
-    const int g_num_cu = y5_num_cu();
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), Gm::NW * 64, Gm::LDS) != hipSuccess || occ < 1) occ = 1;
-    G = (long long)g_num_cu * occ;
-  }
+  long long G = y5_resident_slots(reinterpret_cast<const void*>(kern), Gm::NW * 64, Gm::LDS, max_blocks);
   int th = 0, tw = 0;
   if (!h3_pick_tile(p.B, p.OH, p.OW, Gm::BM, HPMAX, p.tilesN, G, p.SH, &th, &tw))
     return y5_fail(Y5_ERR_UNSUPPORTED, "conv: no spatial tile of this halo configuration fits the layer");
@@ -96,43 +61,18 @@ int launch_h3(const Y5ConvParams& p0, int max_blocks, hipStream_t stream) {
 
 }  // namespace
 
-void y5_h3_cfg_info(int idx, int* bm, int* bn) {
-  const H3Cfg& c = kH3Cfgs[idx < 0 || idx >= kNumH3 ? 0 : idx];
-  *bm = c.wm * c.tm * 32;
-  *bn = c.wn * c.tn * 32;
+int y5_launch_h3_row(const Y5ConvParams& p, int row, int mb, hipStream_t s) {
+  return y5_launch_row(row, "conv: unknown halo 3x3 config", [&](auto i) {
+    constexpr H3Cfg c = kH3Cfgs[decltype(i)::value];
+    return launch_h3<c.wm, c.wn, c.tm, c.tn, c.hpmax, c.nsw>(p, mb, s);
+  }, std::make_index_sequence<y5_num_rows(kH3Cfgs)>{});
 }
 
-int y5_launch_h3_by_cfg(const Y5ConvParams& p, int idx, int mb, hipStream_t s) {
-  switch (idx) {
-    case 0: return launch_h3<2, 2, 5, 2, 496>(p, mb, s);
-    case 1: return launch_h3<2, 2, 5, 1, 496>(p, mb, s);
-    case 2: return launch_h3<2, 2, 7, 2, 512>(p, mb, s);
-    case 3: return launch_h3<2, 2, 4, 2, 400>(p, mb, s);
-    case 4: return launch_h3<2, 2, 7, 1, 512>(p, mb, s);
-    case 5: return launch_h3<2, 2, 4, 1, 400>(p, mb, s);
-    case 6: return launch_h3<2, 4, 5, 1, 496>(p, mb, s);
-    case 7: return launch_h3<2, 4, 7, 1, 512>(p, mb, s);
-    case 8: return launch_h3<2, 4, 4, 1, 400>(p, mb, s);
-    case 9: return launch_h3<4, 2, 2, 2, 400>(p, mb, s);
-    case 10: return launch_h3<4, 1, 4, 4, 512>(p, mb, s);
-    case 11: return launch_h3<4, 2, 4, 2, 512>(p, mb, s);
-    case 12: return launch_h3<2, 2, 4, 2, 320, 4>(p, mb, s);
-    case 13: return launch_h3<2, 2, 4, 1, 320, 4>(p, mb, s);
-    case 14: return launch_h3<2, 2, 3, 2, 320, 4>(p, mb, s);
-    case 15: return launch_h3<4, 2, 2, 2, 320, 4>(p, mb, s);
-    case 16: return launch_h3<4, 2, 2, 1, 320, 4>(p, mb, s);
-    case 17: return launch_h3<2, 2, 1, 2, 320, 4>(p, mb, s);
-    case 18: return launch_h3<4, 2, 1, 2, 592, 4>(p, mb, s);
-    case 19: return launch_h3<2, 2, 2, 2, 592, 4>(p, mb, s);
-  }
-  return y5_fail(Y5_ERR_BAD_ARG, "conv: unknown halo 3x3 config");
-}
-
-// ---- K-streamed pointwise kernel (conv_pwk.h): ids 93 (256-channel N tile), 94 (128) -----------------------------------------------------------
-template <int NT>
+// ---- K-streamed pointwise kernel (conv_pwk.h, kPwkCfgs) -----------------------------------------------------------
+template <int NS, int NT>
 static int launch_pwk(const Y5ConvParams& p, hipStream_t stream) {
-  using Gm = Y5PwkGeom<4, NT>;
-  auto kern = y5_conv_pwk_kernel<4, NT>;
+  using Gm = Y5PwkGeom<NS, NT>;
+  auto kern = y5_conv_pwk_kernel<NS, NT>;
   static bool attr_done = false;
   if (!attr_done) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -143,12 +83,11 @@ static int launch_pwk(const Y5ConvParams& p, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(Gm::NW * 64), Gm::LDS, stream, p);
   return y5_check_launch("y5_conv2d_fwd(pwk)");
 }
-int y5_launch_pwk_by_cfg(const Y5ConvParams& p, int idx, hipStream_t s) {
-  switch (idx) {
-    case 0: return launch_pwk<8>(p, s);
-    case 1: return launch_pwk<4>(p, s);
-  }
-  return y5_fail(Y5_ERR_BAD_ARG, "conv: unknown K-streamed pointwise config");
+int y5_launch_pwk_row(const Y5ConvParams& p, int row, hipStream_t s) {
+  return y5_launch_row(row, "conv: unknown K-streamed pointwise config", [&](auto i) {
+    constexpr PwkCfg c = kPwkCfgs[decltype(i)::value];
+    return launch_pwk<c.ns, c.nt>(p, s);
+  }, std::make_index_sequence<y5_num_rows(kPwkCfgs)>{});
 }
 
 #ifdef Y5_H3_TIMING

@@ -8,6 +8,7 @@
 #include "../../include/yolov5_hip.h"
 #include "conv_pw.h"
 #include "conv_headk.h"
+#include "conv_cfgs.h"
 #include "y5_host.h"
 
 extern "C" int y5_detect_head_fwd_hint(const y5_conv_desc* d, const void* x, const void* w_packed, const float* bias, int ny, int nx, float stride,
@@ -74,7 +75,7 @@ extern "C" int y5_detect_head_fwd_hint(const y5_conv_desc* d, const void* x, con
   if (obj_hint && ((uintptr_t)obj_hint & 15)) return y5_fail(Y5_ERR_BAD_ARG, "detect_head: hint plane must be 16-byte aligned");
 
   // d->cfg == 87: eight waves per workgroup with one stage each (two waves per SIMD under one filter copy); otherwise four waves, two stages
-  const bool w8 = d->cfg == 87;
+  const bool w8 = d->cfg == kCfgPwHeadW8;
   const int nwv = w8 ? 8 : 4;
   const size_t lds = w8 ? y5_conv_pw_lds_bytes<KC, RB, NT, 1, OS, 8>() : y5_conv_pw_lds_bytes<KC, RB, NT, S, OS>();
   auto kern = w8 ? (obj_hint ? y5_conv_pw_head_kernel<KC, RB, NT, 1, OS, true, 8> : y5_conv_pw_head_kernel<KC, RB, NT, 1, OS, false, 8>)
@@ -88,13 +89,7 @@ extern "C" int y5_detect_head_fwd_hint(const y5_conv_desc* d, const void* x, con
     attr_done = true;
   }
   const long long nbt = ((long long)(p.M >> 5) + nwv - 1) / nwv;
-  long long G = d->max_blocks;
-  if (G <= 0) {
-    const int num_cu = y5_num_cu();
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), nwv * 64, lds) != hipSuccess || occ < 1) occ = 1;
-    G = (long long)num_cu * occ;
-  }
+  long long G = y5_resident_slots(reinterpret_cast<const void*>(kern), nwv * 64, lds, d->max_blocks);
   if (G > nbt) G = nbt;
   if (G >= 8) G &= ~7LL;
   hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(nwv * 64), lds, static_cast<hipStream_t>(stream_), p, h);
