@@ -6,6 +6,8 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
+#include <variant>
 #include <vector>
 
 #include "../../include/yolov5_hip.h"
@@ -71,19 +73,119 @@ int y5_num_cu() {
 // ---------------------------------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------------------------------
-enum OpKind { OP_CONV, OP_TO_NHWC, OP_SPPF, OP_UPS, OP_COPY, OP_DECODE, OP_TO_NCHW, OP_STEM, OP_HEAD, OP_NOP, OP_BNECK, OP_K3PW, OP_BNECK_CV3, OP_FRONT, OP_SPPF_FRONT };
+// One argument record per op kind.  Its fields are the parameters of the entry point the op launches, under that entry point's names
+// (include/yolov5_hip.h); run() hands them on.  outputs() names, once, the pointers y5_plan_rebind_output may re-point: the main output,
+// the second output and the objectness plane -- an input never appears there.
+struct ConvArgs {
+  y5_conv_desc d; const void* x; const void* w_packed; const float* bias; const void* residual; void* y; void* y_up2;
+  template <class F> void outputs(F&& f) { f(y); f(y_up2); }
+};
+struct ToNhwcArgs {
+  const void* src; int src_dtype; void* dst; int dst_dtype, B, C, H, W, ld; float scale;
+  template <class F> void outputs(F&& f) { f(dst); }
+};
+struct ToNchwArgs {
+  const void* src; int dtype; void* dst; int B, C, H, W, ld;
+  template <class F> void outputs(F&& f) { f(dst); }
+};
+struct SppfPoolArgs {
+  void* buf; int dtype, B, H, W, C, ld, k;
+  template <class F> void outputs(F&& f) { f(buf); }
+};
+struct UpsampleArgs {
+  const void* src; int dtype; void* dst; int B, H, W, C, lds, ldd;
+  template <class F> void outputs(F&& f) { f(dst); }
+};
+struct CopyArgs {
+  const void* src; int dtype; void* dst; int npix, C, lds, ldd;
+  template <class F> void outputs(F&& f) { f(dst); }
+};
+// what the Detect decode and the fused head share: the anchors by value (y5_plan_set_anchors) and the objectness plane (y5_plan_set_obj_hint)
+struct DetectTail { float anchors_px[16]; void* obj_hint; };
+struct DecodeArgs : DetectTail {
+  const void* logits; int dtype, B, ny, nx, na, no, nm, ld; float stride; void* z; int z_dtype; long long nrows_total, row_off; void* raw;
+  template <class F> void outputs(F&& f) { f(z); f(raw); f(obj_hint); }
+};
+struct HeadArgs : DetectTail {
+  y5_conv_desc d; const void* x; const void* w_packed; const float* bias; int ny, nx; float stride; void* z; long long nrows_total, row_off;
+  template <class F> void outputs(F&& f) { f(z); f(obj_hint); }
+};
+struct StemArgs {
+  const void* x_nchw; int B, H, W; const void* w_stem; const float* bias; int C2, Npad; void* y; int ldy;
+  template <class F> void outputs(F&& f) { f(y); }
+};
+struct NopArgs {
+  template <class F> void outputs(F&&) {}
+};
+struct BneckArgs {
+  const void* x; int ldx; const void* w1_packed; const float* bias1; int Kpad1; const void* w2_packed; const float* bias2; int Kpad2; void* y;
+  int ldy, B, H, W, C, add;
+  template <class F> void outputs(F&& f) { f(y); }
+};
+struct K3pwArgs {
+  y5_conv_desc d; const void* x; const void* w1_packed; const float* bias1; const void* w2_packed; const float* bias2; int C3, Npad2, Kpad2, act2;
+  void* y; int ldy; void* y2; int ld2, split_n;
+  template <class F> void outputs(F&& f) { f(y); f(y2); }
+};
+struct BneckCv3Args {
+  const void* x; int ldx; const void* w1_packed; const float* bias1; int Kpad1; const void* w2_packed; const float* bias2; int Kpad2; const void* y2;
+  int ld2; const void* w3_packed; const float* bias3; int Kpad3, C3, act3; void* out; int ldo, B, H, W, C, add;
+  template <class F> void outputs(F&& f) { f(out); }
+};
+struct FrontArgs {
+  const void* x_nchw; int B, H, W; const void* w_stem; const float* bias0; int C0; const void* w1_packed; const float* bias1; int C1, Npad1, Kpad1, act1;
+  const void* w2_packed; const float* bias2; int C3, Npad2, Kpad2, act2; void* y; int ldy; void* y2; int ld2, split_n;
+  template <class F> void outputs(F&& f) { f(y); f(y2); }
+};
+struct SppfFrontArgs {
+  const void* x; int ldx; const void* w_packed; const float* bias; int Kpad; void* buf; int ld, B, H, W, C1, c_, k, act;
+  template <class F> void outputs(F&& f) { f(buf); }
+};
+
+static int run(const ConvArgs& a, void* st) { return y5_conv2d_fwd(&a.d, a.x, a.w_packed, a.bias, a.residual, a.y, a.y_up2, st); }
+static int run(const ToNhwcArgs& a, void* st) { return y5_nchw_to_nhwc(a.src, a.src_dtype, a.dst, a.dst_dtype, a.B, a.C, a.H, a.W, a.ld, a.scale, st); }
+static int run(const ToNchwArgs& a, void* st) { return y5_nhwc_to_nchw(a.src, a.dtype, a.dst, a.B, a.C, a.H, a.W, a.ld, st); }
+static int run(const SppfPoolArgs& a, void* st) { return y5_sppf_pool(a.buf, a.dtype, a.B, a.H, a.W, a.C, a.ld, a.k, st); }
+static int run(const UpsampleArgs& a, void* st) { return y5_upsample2x(a.src, a.dtype, a.dst, a.B, a.H, a.W, a.C, a.lds, a.ldd, st); }
+static int run(const CopyArgs& a, void* st) { return y5_copy_slice(a.src, a.dtype, a.dst, a.npix, a.C, a.lds, a.ldd, st); }
+static int run(const DecodeArgs& a, void* st) {
+  return y5_detect_decode_hint(a.logits, a.dtype, a.B, a.ny, a.nx, a.na, a.no, a.nm, a.ld, a.stride, a.anchors_px, a.z, a.z_dtype, a.nrows_total, a.row_off,
+                               a.raw, a.obj_hint, st);
+}
+static int run(const HeadArgs& a, void* st) {
+  return y5_detect_head_fwd_hint(&a.d, a.x, a.w_packed, a.bias, a.ny, a.nx, a.stride, a.anchors_px, a.z, a.nrows_total, a.row_off, a.obj_hint, st);
+}
+static int run(const StemArgs& a, void* st) { return y5_conv_stem_fwd(a.x_nchw, a.B, a.H, a.W, a.w_stem, a.bias, a.C2, a.Npad, a.y, a.ldy, 0, st); }
+static int run(const NopArgs&, void*) { return Y5_OK; }
+static int run(const BneckArgs& a, void* st) {
+  return y5_bottleneck_fwd(a.x, a.ldx, a.w1_packed, a.bias1, a.Kpad1, a.w2_packed, a.bias2, a.Kpad2, a.y, a.ldy, a.B, a.H, a.W, a.C, a.add, 0, st);
+}
+static int run(const K3pwArgs& a, void* st) {
+  return y5_conv_k3pw_fwd(&a.d, a.x, a.w1_packed, a.bias1, a.w2_packed, a.bias2, a.C3, a.Npad2, a.Kpad2, a.act2, a.y, a.ldy, a.y2, a.ld2, a.split_n, st);
+}
+static int run(const BneckCv3Args& a, void* st) {
+  return y5_bottleneck_cv3_fwd(a.x, a.ldx, a.w1_packed, a.bias1, a.Kpad1, a.w2_packed, a.bias2, a.Kpad2, a.y2, a.ld2, a.w3_packed, a.bias3, a.Kpad3, a.C3,
+                               a.act3, a.out, a.ldo, a.B, a.H, a.W, a.C, a.add, 0, st);
+}
+static int run(const FrontArgs& a, void* st) {
+  return y5_conv_front_fwd(a.x_nchw, a.B, a.H, a.W, a.w_stem, a.bias0, a.C0, a.w1_packed, a.bias1, a.C1, a.Npad1, a.Kpad1, a.act1, a.w2_packed, a.bias2, a.C3,
+                           a.Npad2, a.Kpad2, a.act2, a.y, a.ldy, a.y2, a.ld2, a.split_n, 0, st);
+}
+static int run(const SppfFrontArgs& a, void* st) {
+  return y5_sppf_cv1_pool_fwd(a.x, a.ldx, a.w_packed, a.bias, a.Kpad, a.buf, a.ld, a.B, a.H, a.W, a.C1, a.c_, a.k, a.act, st);
+}
+
+using OpArgs = std::variant<NopArgs, ConvArgs, ToNhwcArgs, ToNchwArgs, SppfPoolArgs, UpsampleArgs, CopyArgs, DecodeArgs, HeadArgs, StemArgs, BneckArgs, K3pwArgs,
+                            BneckCv3Args, FrontArgs, SppfFrontArgs>;
 
 struct Op {
-  OpKind kind;
-  y5_conv_desc conv;
-  const void* p0; const void* p1; const void* p2; const void* p3; void* q0; void* q1;
-  const void* r0; const void* r1; const void* r2;  // further read-only operands (OP_BNECK_CV3: y2, w3, bias3)
-  int i[16];
-  float f[2];
-  long long l[2];
-  float anchors[16];
   int branch;  // 0: the caller's stream; 1: the plan's side stream (forked after the preceding main op, joined at the end of the range)
+  OpArgs args;
 };
+
+static int run_op(const Op& o, void* st) {
+  return std::visit([st](const auto& a) { return run(a, st); }, o.args);
+}
 
 struct GraphEntry { unsigned long long key; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
 
@@ -97,6 +199,20 @@ struct y5_plan {
   std::vector<hipEvent_t> events;    // fork / join markers, one per fork point of a run + one join
   bool flat = false;                 // run every op on the caller's stream (per-op timing: no fork / join latency in the figure)
 };
+
+static int plan_push(y5_plan* pl, OpArgs args) {
+  pl->ops.push_back(Op{0, std::move(args)});
+  return Y5_OK;
+}
+static Op* plan_op(y5_plan* pl, int op) { return pl && op >= 0 && op < (int)pl->ops.size() ? &pl->ops[op] : nullptr; }
+// the Detect decode / fused head part of op `op`, or null
+static DetectTail* plan_detect_tail(y5_plan* pl, int op) {
+  Op* o = plan_op(pl, op);
+  if (!o) return nullptr;
+  if (auto* a = std::get_if<DecodeArgs>(&o->args)) return a;
+  if (auto* a = std::get_if<HeadArgs>(&o->args)) return a;
+  return nullptr;
+}
 
 extern "C" y5_plan* y5_plan_create(void) { return new y5_plan(); }
 extern "C" void y5_plan_destroy(y5_plan* p) {
@@ -114,64 +230,57 @@ extern "C" int y5_plan_size(const y5_plan* p) { return p ? (int)p->ops.size() : 
 extern "C" int y5_plan_add_conv(y5_plan* pl, const y5_conv_desc* d, const void* x, const void* w, const float* bias,
                                 const void* res, void* y, void* y2) {
   if (!pl || !d) return y5_fail(Y5_ERR_BAD_ARG, "plan_add_conv: null");
-  Op o{}; o.kind = OP_CONV; o.conv = *d; o.p0 = x; o.p1 = w; o.p2 = bias; o.p3 = res; o.q0 = y; o.q1 = y2;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  ConvArgs a{};
+  a.d = *d; a.x = x; a.w_packed = w; a.bias = bias; a.residual = res; a.y = y; a.y_up2 = y2;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_nchw_to_nhwc(y5_plan* pl, const void* src, int sdt, void* dst, int ddt, int B, int C, int H, int W,
                                         int ld, float scale) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_TO_NHWC; o.p0 = src; o.q0 = dst;
-  o.i[0] = sdt; o.i[1] = ddt; o.i[2] = B; o.i[3] = C; o.i[4] = H; o.i[5] = W; o.i[6] = ld; o.f[0] = scale;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  ToNhwcArgs a{};
+  a.src = src; a.src_dtype = sdt; a.dst = dst; a.dst_dtype = ddt; a.B = B; a.C = C; a.H = H; a.W = W; a.ld = ld; a.scale = scale;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_nhwc_to_nchw(y5_plan* pl, const void* src, int dt, void* dst, int B, int C, int H, int W, int ld) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_TO_NCHW; o.p0 = src; o.q0 = dst;
-  o.i[0] = dt; o.i[1] = B; o.i[2] = C; o.i[3] = H; o.i[4] = W; o.i[5] = ld;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  ToNchwArgs a{};
+  a.src = src; a.dtype = dt; a.dst = dst; a.B = B; a.C = C; a.H = H; a.W = W; a.ld = ld;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_sppf_cv1_pool(y5_plan* pl, const void* x, int ldx, const void* w, const float* bias, int Kpad, void* buf, int ld, int B, int H, int W,
                                          int C1, int c_, int k, int act) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_SPPF_FRONT; o.p0 = x; o.p1 = w; o.p2 = bias; o.q0 = buf;
-  o.i[0] = ldx; o.i[1] = Kpad; o.i[2] = ld; o.i[3] = B; o.i[4] = H; o.i[5] = W; o.i[6] = C1; o.i[7] = c_; o.i[8] = k; o.i[9] = act;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  SppfFrontArgs a{};
+  a.x = x; a.ldx = ldx; a.w_packed = w; a.bias = bias; a.Kpad = Kpad; a.buf = buf; a.ld = ld; a.B = B; a.H = H; a.W = W; a.C1 = C1; a.c_ = c_; a.k = k; a.act = act;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_sppf_pool(y5_plan* pl, void* buf, int dt, int B, int H, int W, int C, int ld, int k) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_SPPF; o.q0 = buf;
-  o.i[0] = dt; o.i[1] = B; o.i[2] = H; o.i[3] = W; o.i[4] = C; o.i[5] = ld; o.i[6] = k;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  SppfPoolArgs a{};
+  a.buf = buf; a.dtype = dt; a.B = B; a.H = H; a.W = W; a.C = C; a.ld = ld; a.k = k;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_upsample2x(y5_plan* pl, const void* src, int dt, void* dst, int B, int H, int W, int C, int lds, int ldd) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_UPS; o.p0 = src; o.q0 = dst;
-  o.i[0] = dt; o.i[1] = B; o.i[2] = H; o.i[3] = W; o.i[4] = C; o.i[5] = lds; o.i[6] = ldd;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  UpsampleArgs a{};
+  a.src = src; a.dtype = dt; a.dst = dst; a.B = B; a.H = H; a.W = W; a.C = C; a.lds = lds; a.ldd = ldd;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_copy_slice(y5_plan* pl, const void* src, int dt, void* dst, int npix, int C, int lds, int ldd) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_COPY; o.p0 = src; o.q0 = dst;
-  o.i[0] = dt; o.i[1] = npix; o.i[2] = C; o.i[3] = lds; o.i[4] = ldd;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  CopyArgs a{};
+  a.src = src; a.dtype = dt; a.dst = dst; a.npix = npix; a.C = C; a.lds = lds; a.ldd = ldd;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_detect_decode(y5_plan* pl, const void* logits, int dt, int B, int ny, int nx, int na, int no, int nm, int ld,
                                          float stride, const float* anchors_px, void* z, int zdt, long long nrows_total,
                                          long long row_off, void* raw) {
   if (!pl || !anchors_px || na > 8) return y5_fail(Y5_ERR_BAD_ARG, "plan: null / na");
-  Op o{}; o.kind = OP_DECODE; o.p0 = logits; o.q0 = z; o.q1 = raw;
-  o.i[0] = dt; o.i[1] = B; o.i[2] = ny; o.i[3] = nx; o.i[4] = na; o.i[5] = no; o.i[6] = nm; o.i[7] = ld; o.i[8] = zdt;
-  o.f[0] = stride; o.l[0] = nrows_total; o.l[1] = row_off;
-  for (int k = 0; k < na * 2; ++k) o.anchors[k] = anchors_px[k];
-  pl->ops.push_back(o);
-  return Y5_OK;
+  DecodeArgs a{};
+  a.logits = logits; a.dtype = dt; a.B = B; a.ny = ny; a.nx = nx; a.na = na; a.no = no; a.nm = nm; a.ld = ld; a.stride = stride; a.z = z; a.z_dtype = zdt;
+  a.nrows_total = nrows_total; a.row_off = row_off; a.raw = raw;
+  for (int k = 0; k < na * 2; ++k) a.anchors_px[k] = anchors_px[k];
+  return plan_push(pl, a);
 }
 
 // fused Detect head (head.hip): the convolution `d` + the decode of one level; y5_plan_add_nop keeps the op numbering of the
@@ -179,76 +288,72 @@ extern "C" int y5_plan_add_detect_decode(y5_plan* pl, const void* logits, int dt
 extern "C" int y5_plan_add_detect_head(y5_plan* pl, const y5_conv_desc* d, const void* x, const void* w, const float* bias, int ny, int nx,
                                        float stride, const float* anchors_px, void* z, long long nrows_total, long long row_off) {
   if (!pl || !d || !anchors_px) return y5_fail(Y5_ERR_BAD_ARG, "plan_add_detect_head: null");
-  Op o{}; o.kind = OP_HEAD; o.conv = *d; o.p0 = x; o.p1 = w; o.p2 = bias; o.q0 = z;
-  o.i[0] = ny; o.i[1] = nx; o.f[0] = stride; o.l[0] = nrows_total; o.l[1] = row_off;
-  for (int k = 0; k < 6; ++k) o.anchors[k] = anchors_px[k];
-  pl->ops.push_back(o);
-  return Y5_OK;
+  HeadArgs a{};
+  a.d = *d; a.x = x; a.w_packed = w; a.bias = bias; a.ny = ny; a.nx = nx; a.stride = stride; a.z = z; a.nrows_total = nrows_total; a.row_off = row_off;
+  for (int k = 0; k < 6; ++k) a.anchors_px[k] = anchors_px[k];
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_bottleneck(y5_plan* pl, const void* x, int ldx, const void* w1, const float* b1, int Kpad1, const void* w2, const float* b2,
                                       int Kpad2, void* y, int ldy, int B, int H, int W, int C, int add) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_BNECK; o.p0 = x; o.p1 = w1; o.p2 = b1; o.p3 = w2; o.q0 = y; o.q1 = const_cast<float*>(b2);
-  o.i[0] = ldx; o.i[1] = Kpad1; o.i[2] = Kpad2; o.i[3] = ldy; o.i[4] = B; o.i[5] = H; o.i[6] = W; o.i[7] = C; o.i[8] = add;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  BneckArgs a{};
+  a.x = x; a.ldx = ldx; a.w1_packed = w1; a.bias1 = b1; a.Kpad1 = Kpad1; a.w2_packed = w2; a.bias2 = b2; a.Kpad2 = Kpad2; a.y = y; a.ldy = ldy;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.add = add;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_conv_k3pw(y5_plan* pl, const y5_conv_desc* d, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                                      int C3, int Npad2, int Kpad2, int act2, void* y, int ldy, void* y2, int ld2, int split_n) {
   if (!pl || !d) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_K3PW; o.conv = *d; o.p0 = x; o.p1 = w1; o.p2 = b1; o.p3 = w2; o.q0 = y; o.q1 = y2;
-  o.l[0] = (long long)(uintptr_t)b2;
-  o.i[0] = C3; o.i[1] = Npad2; o.i[2] = Kpad2; o.i[3] = act2; o.i[4] = ldy; o.i[5] = ld2; o.i[6] = split_n;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  K3pwArgs a{};
+  a.d = *d; a.x = x; a.w1_packed = w1; a.bias1 = b1; a.w2_packed = w2; a.bias2 = b2; a.C3 = C3; a.Npad2 = Npad2; a.Kpad2 = Kpad2; a.act2 = act2;
+  a.y = y; a.ldy = ldy; a.y2 = y2; a.ld2 = ld2; a.split_n = split_n;
+  return plan_push(pl, a);
 }
 // Detect decode / fused head op `op`: also write every row's objectness to `hint` ((B, nrows_total), z's dtype) -- the NMS filter's shortcut
 extern "C" int y5_plan_set_obj_hint(y5_plan* pl, int op, void* hint) {
-  if (!pl || op < 0 || op >= (int)pl->ops.size() || (pl->ops[op].kind != OP_DECODE && pl->ops[op].kind != OP_HEAD))
-    return y5_fail(Y5_ERR_BAD_ARG, "plan_set_obj_hint: not a Detect decode / fused head op");
-  pl->ops[op].p3 = hint;
+  DetectTail* t = plan_detect_tail(pl, op);
+  if (!t) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_obj_hint: not a Detect decode / fused head op");
+  t->obj_hint = hint;
   return Y5_OK;
 }
 extern "C" int y5_plan_add_bottleneck_cv3(y5_plan* pl, const void* x, int ldx, const void* w1, const float* b1, int Kpad1, const void* w2, const float* b2,
                                           int Kpad2, const void* y2, int ld2, const void* w3, const float* b3, int Kpad3, int C3, int act3, void* out, int ldo,
                                           int B, int H, int W, int C, int add) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_BNECK_CV3; o.p0 = x; o.p1 = w1; o.p2 = b1; o.p3 = w2; o.q0 = out; o.q1 = const_cast<float*>(b2);
-  o.r0 = y2; o.r1 = w3; o.r2 = b3;
-  o.i[0] = ldx; o.i[1] = Kpad1; o.i[2] = Kpad2; o.i[3] = ldo; o.i[4] = B; o.i[5] = H; o.i[6] = W; o.i[7] = C; o.i[8] = add;
-  o.i[9] = ld2; o.i[10] = Kpad3; o.i[11] = C3 | (act3 ? 1 << 16 : 0);
-  pl->ops.push_back(o);
-  return Y5_OK;
+  BneckCv3Args a{};
+  a.x = x; a.ldx = ldx; a.w1_packed = w1; a.bias1 = b1; a.Kpad1 = Kpad1; a.w2_packed = w2; a.bias2 = b2; a.Kpad2 = Kpad2; a.y2 = y2; a.ld2 = ld2;
+  a.w3_packed = w3; a.bias3 = b3; a.Kpad3 = Kpad3; a.C3 = C3; a.act3 = act3; a.out = out; a.ldo = ldo; a.B = B; a.H = H; a.W = W; a.C = C; a.add = add;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_conv_front(y5_plan* pl, const void* x_nchw, int B, int H, int W, const void* w_stem, const float* bias0, int C0, const void* w1,
                                       const float* bias1, int C1, int Npad1, int Kpad1, int act1, const void* w2, const float* bias2, int C3, int Npad2,
                                       int Kpad2, int act2, void* y, int ldy, void* y2, int ld2, int split_n) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_FRONT; o.p0 = x_nchw; o.p1 = w_stem; o.p2 = bias0; o.p3 = w1; o.r0 = bias1; o.r1 = w2; o.r2 = bias2; o.q0 = y; o.q1 = y2;
-  o.i[0] = B; o.i[1] = H; o.i[2] = W; o.i[3] = C0; o.i[4] = C1; o.i[5] = Npad1; o.i[6] = Kpad1; o.i[7] = act1; o.i[8] = C3; o.i[9] = Npad2; o.i[10] = Kpad2;
-  o.i[11] = act2; o.i[12] = ldy; o.i[13] = ld2; o.i[14] = split_n;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  FrontArgs a{};
+  a.x_nchw = x_nchw; a.B = B; a.H = H; a.W = W; a.w_stem = w_stem; a.bias0 = bias0; a.C0 = C0; a.w1_packed = w1; a.bias1 = bias1; a.C1 = C1; a.Npad1 = Npad1;
+  a.Kpad1 = Kpad1; a.act1 = act1; a.w2_packed = w2; a.bias2 = bias2; a.C3 = C3; a.Npad2 = Npad2; a.Kpad2 = Kpad2; a.act2 = act2; a.y = y; a.ldy = ldy;
+  a.y2 = y2; a.ld2 = ld2; a.split_n = split_n;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_nop(y5_plan* pl) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_NOP;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  return plan_push(pl, NopArgs{});
 }
 
 extern "C" int y5_plan_add_conv_stem(y5_plan* pl, const void* x_nchw, int B, int H, int W, const void* w_stem, const float* bias,
                                      int C2, int Npad, void* y, int ldy) {
   if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan: null");
-  Op o{}; o.kind = OP_STEM; o.p0 = x_nchw; o.p1 = w_stem; o.p2 = bias; o.q0 = y;
-  o.i[0] = B; o.i[1] = H; o.i[2] = W; o.i[3] = C2; o.i[4] = Npad; o.i[5] = ldy;
-  pl->ops.push_back(o);
-  return Y5_OK;
+  StemArgs a{};
+  a.x_nchw = x_nchw; a.B = B; a.H = H; a.W = W; a.w_stem = w_stem; a.bias = bias; a.C2 = C2; a.Npad = Npad; a.y = y; a.ldy = ldy;
+  return plan_push(pl, a);
 }
 extern "C" int y5_plan_set_input(y5_plan* pl, int op, const void* src) {
-  if (!pl || op < 0 || op >= (int)pl->ops.size()) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_input: bad op index");
-  if (pl->ops[op].kind != OP_STEM && pl->ops[op].kind != OP_TO_NHWC && pl->ops[op].kind != OP_FRONT) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_input: op does not read the model input");
-  pl->ops[op].p0 = src;
+  Op* o = plan_op(pl, op);
+  if (!o) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_input: bad op index");
+  if (auto* a = std::get_if<StemArgs>(&o->args)) a->x_nchw = src;
+  else if (auto* a = std::get_if<ToNhwcArgs>(&o->args)) a->src = src;
+  else if (auto* a = std::get_if<FrontArgs>(&o->args)) a->x_nchw = src;
+  else return y5_fail(Y5_ERR_BAD_ARG, "plan_set_input: op does not read the model input");
   return Y5_OK;
 }
 
@@ -257,12 +362,10 @@ extern "C" int y5_plan_set_input(y5_plan* pl, int op, const void* src) {
 extern "C" int y5_plan_rebind_output(y5_plan* pl, int first, int last, const void* old_ptr, void* new_ptr) {
   if (!pl || first < 0 || last > (int)pl->ops.size() || first > last || !old_ptr || !new_ptr) return y5_fail(Y5_ERR_BAD_ARG, "plan_rebind_output: bad args");
   int n = 0;
-  for (int k = first; k < last; ++k) {
-    Op& o = pl->ops[k];
-    if (o.q0 == old_ptr) { o.q0 = new_ptr; ++n; }
-    if (o.q1 == old_ptr && o.kind != OP_BNECK && o.kind != OP_BNECK_CV3) { o.q1 = new_ptr; ++n; }
-    if (o.p3 == old_ptr && (o.kind == OP_DECODE || o.kind == OP_HEAD)) { o.p3 = new_ptr; ++n; }  // objectness hint plane (y5_plan_set_obj_hint)
-  }
+  auto repoint = [&](void*& p) {
+    if (p == old_ptr) { p = new_ptr; ++n; }
+  };
+  for (int k = first; k < last; ++k) std::visit([&](auto& a) { a.outputs(repoint); }, pl->ops[k].args);
   if (!n) return y5_fail(Y5_ERR_BAD_ARG, "plan_rebind_output: no op writes that pointer");
   return Y5_OK;
 }
@@ -287,56 +390,26 @@ extern "C" int y5_plan_select_graph(y5_plan* pl, unsigned long long key) {
 // New anchor sizes (pixels) for a Detect decode / fused head op: Detect.anchors is a buffer the EMA interpolates like any other
 // (utils/torch_utils.py:361-365), so a refreshed plan must pick it up together with the filters.
 extern "C" int y5_plan_set_anchors(y5_plan* pl, int op, const float* anchors_px, int n) {
-  if (!pl || op < 0 || op >= (int)pl->ops.size() || !anchors_px || n < 1 || n > 16) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_anchors: bad args");
-  Op& o = pl->ops[op];
-  if (o.kind != OP_DECODE && o.kind != OP_HEAD) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_anchors: op has no anchors");
-  for (int k = 0; k < n; ++k) o.anchors[k] = anchors_px[k];
+  if (!plan_op(pl, op) || !anchors_px || n < 1 || n > 16) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_anchors: bad args");
+  DetectTail* t = plan_detect_tail(pl, op);
+  if (!t) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_anchors: op has no anchors");
+  for (int k = 0; k < n; ++k) t->anchors_px[k] = anchors_px[k];
   return Y5_OK;
 }
 
-static int run_op(const Op& o, void* st) {
-  switch (o.kind) {
-    case OP_STEM: return y5_conv_stem_fwd(o.p0, o.i[0], o.i[1], o.i[2], o.p1, (const float*)o.p2, o.i[3], o.i[4], o.q0, o.i[5], 0, st);
-    case OP_CONV: return y5_conv2d_fwd(&o.conv, o.p0, o.p1, (const float*)o.p2, o.p3, o.q0, o.q1, st);
-    case OP_TO_NHWC: return y5_nchw_to_nhwc(o.p0, o.i[0], o.q0, o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.i[6], o.f[0], st);
-    case OP_TO_NCHW: return y5_nhwc_to_nchw(o.p0, o.i[0], o.q0, o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], st);
-    case OP_SPPF: return y5_sppf_pool(o.q0, o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.i[6], st);
-    case OP_UPS: return y5_upsample2x(o.p0, o.i[0], o.q0, o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.i[6], st);
-    case OP_COPY: return y5_copy_slice(o.p0, o.i[0], o.q0, o.i[1], o.i[2], o.i[3], o.i[4], st);
-    case OP_HEAD:
-      return y5_detect_head_fwd_hint(&o.conv, o.p0, o.p1, (const float*)o.p2, o.i[0], o.i[1], o.f[0], o.anchors, o.q0, o.l[0], o.l[1], const_cast<void*>(o.p3), st);
-    case OP_NOP: return Y5_OK;
-    case OP_SPPF_FRONT:
-      return y5_sppf_cv1_pool_fwd(o.p0, o.i[0], o.p1, (const float*)o.p2, o.i[1], o.q0, o.i[2], o.i[3], o.i[4], o.i[5], o.i[6], o.i[7], o.i[8], o.i[9], st);
-    case OP_BNECK_CV3:
-      return y5_bottleneck_cv3_fwd(o.p0, o.i[0], o.p1, (const float*)o.p2, o.i[1], o.p3, (const float*)o.q1, o.i[2], o.r0, o.i[9], o.r1, (const float*)o.r2,
-                                   o.i[10], o.i[11] & 0xffff, o.i[11] >> 16, o.q0, o.i[3], o.i[4], o.i[5], o.i[6], o.i[7], o.i[8], 0, st);
-    case OP_FRONT:
-      return y5_conv_front_fwd(o.p0, o.i[0], o.i[1], o.i[2], o.p1, (const float*)o.p2, o.i[3], o.p3, (const float*)o.r0, o.i[4], o.i[5], o.i[6], o.i[7], o.r1,
-                               (const float*)o.r2, o.i[8], o.i[9], o.i[10], o.i[11], o.q0, o.i[12], o.q1, o.i[13], o.i[14], 0, st);
-    case OP_K3PW:
-      return y5_conv_k3pw_fwd(&o.conv, o.p0, o.p1, (const float*)o.p2, o.p3, (const float*)(uintptr_t)o.l[0], o.i[0], o.i[1], o.i[2], o.i[3], o.q0, o.i[4],
-                              o.q1, o.i[5], o.i[6], st);
-    case OP_BNECK:
-      return y5_bottleneck_fwd(o.p0, o.i[0], o.p1, (const float*)o.p2, o.i[1], o.p3, (const float*)o.q1, o.i[2], o.q0, o.i[3], o.i[4], o.i[5], o.i[6],
-                               o.i[7], o.i[8], 0, st);
-    case OP_DECODE:
-      return y5_detect_decode_hint(o.p0, o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.i[6], o.i[7], o.f[0], o.anchors, o.q0, o.i[8],
-                                   o.l[0], o.l[1], o.q1, const_cast<void*>(o.p3), st);
-  }
-  return y5_fail(Y5_ERR_BAD_ARG, "plan: unknown op");
-}
-
 extern "C" int y5_plan_set_branch(y5_plan* pl, int op, int branch) {
-  if (!pl || op < 0 || op >= (int)pl->ops.size() || branch < 0 || branch > 1) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_branch: bad op index / branch");
-  pl->ops[op].branch = branch;
+  Op* o = plan_op(pl, op);
+  if (!o || branch < 0 || branch > 1) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_branch: bad op index / branch");
+  o->branch = branch;
   return Y5_OK;
 }
 
 extern "C" int y5_plan_set_conv_cfg(y5_plan* pl, int op, int cfg) {
-  if (!pl || op < 0 || op >= (int)pl->ops.size() || pl->ops[op].kind != OP_CONV) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_conv_cfg: not a convolution op");
+  Op* o = plan_op(pl, op);
+  ConvArgs* a = o ? std::get_if<ConvArgs>(&o->args) : nullptr;
+  if (!a) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_conv_cfg: not a convolution op");
   if (pl->graph || !pl->cache.empty()) return y5_fail(Y5_ERR_BAD_ARG, "plan_set_conv_cfg: the plan has captured graphs");
-  pl->ops[op].conv.cfg = cfg;
+  a->d.cfg = cfg;
   return Y5_OK;
 }
 

@@ -744,6 +744,9 @@ class Engine:
         self._stem_args = None
         self._front = None     # plan index of the fused backbone front (conv_front.h: stem + 1.Conv + 2.C3.cv1+cv2), appended after the stem op
         self._front_args = None
+        self._k3pw_skip = -1   # spec op multiplied inside the launch in front of it (conv + pointwise, Bottleneck + cv3): added as a no-op
+        self._graph_gen = 0    # bumped when captured graphs go stale (new anchors): part of the binding key
+        self._stem_active = False  # the latest forward read an fp16 NCHW batch through the stem / front op
         with torch.no_grad():
             self._fused_heads = set()
             for k, op in enumerate(self.spec.ops):
@@ -796,6 +799,54 @@ class Engine:
     def _ld(self, t: TRef):
         return self.spec.bufs[t.buf].C
 
+    def _time_scratch_plan(self, ops, iters, refusal_ok=False):
+        """Milliseconds y5_plan_time_range reports for `iters` runs of a scratch plan made of `ops` = [(y5_plan_add_* function, its arguments behind the
+        plan)]; the plan is destroyed whatever happens.  refusal_ok: a status other than 0 (a shape outside a fused kernel's range) gives None;
+        otherwise it raises through _lib.check."""
+        lib = self.lib
+        plan = C.c_void_p(lib.y5_plan_create())
+
+        def ok(rc):
+            if rc != 0 and not refusal_ok:
+                _lib.check(rc, lib)
+            return rc == 0
+
+        try:
+            ms = C.c_float(0)
+            if all(ok(add(plan, *args)) for add, args in ops) and ok(lib.y5_plan_time_range(plan, 0, len(ops), iters, self._stream(), C.byref(ms))):
+                return ms.value
+            return None
+        finally:
+            lib.y5_plan_destroy(plan)
+
+    def _pick_build(self, key, cands, time_build):
+        """Which build of a fused kernel (configuration ids `cands`) is fastest for a shape: (cfg, ms), or None when the library takes none of them.
+        time_build(cfg, known) -> ms | None.  The choice is kept in the tile-choice cache under `key` like any other race -- timed once per shape, the same in
+        every later plan: with a stored choice only that build is timed.  Strictly less wins, so a tie keeps the first candidate."""
+        _load_tune_cache()
+        known = _TUNE_CACHE.get(key)
+        best = None
+        for cfg in ((known[0],) if known is not None and known[0] in cands else cands):
+            ms = time_build(cfg, known is not None)
+            if ms is not None and (best is None or ms < best[1]):
+                best = (cfg, ms)
+        if best is not None and known is None:
+            _TUNE_CACHE[key] = (best[0], -1)
+            _save_tune_cache()
+        return best
+
+    def _plan_ranges(self, nchw16):
+        """[(first, last)] of the plan ops one forward launches, in order.  nchw16: an fp16 NCHW batch, which the stem reads in place (no NHWC repack pass) --
+        the stem op, then the plan from op 2; or, with the fused front (stem + 1.Conv + 2.C3.cv1+cv2 in one launch), that op, then the plan from op 4.
+        Any other input: the plan behind the repack of op 0, which __call__ launches itself."""
+        if self._stem is None:
+            return [(1, self.lib.y5_plan_size(self.plan))]
+        if not nchw16:
+            return [(1, self._stem)]
+        if self._front is not None:
+            return [(self._front, self._front + 1), (4, self._stem)]
+        return [(self._stem, self._stem + 1), (2, self._stem)]
+
     def _add(self, op):
         lib, B, kind = self.lib, self.spec.B, op["op"]
         if kind == "to_nhwc":
@@ -803,7 +854,7 @@ class Engine:
             self._first_op = (d, op["C"])
             rc = lib.y5_plan_add_nchw_to_nhwc(self.plan, None, self.dt, self._ptr(d), self.dt, B, op["C"], d.H, d.W, self._ld(d), 1.0)
             self.op_names.append("to_nhwc")
-        elif kind == "conv" and getattr(self, "_k3pw_skip", -1) == self._cur:
+        elif kind == "conv" and self._k3pw_skip == self._cur:
             rc = lib.y5_plan_add_nop(self.plan)  # multiplied inside the 3x3 in front of it (y5_plan_add_conv_k3pw)
             self.conv_cfgs.append(-2)
             self.op_names.append("conv:" + op["name"] + "(fused)")
@@ -900,7 +951,7 @@ class Engine:
                     _lib.check(self.lib.y5_plan_set_anchors(self.plan, idx, (C.c_float * len(apx))(*apx), len(apx)), self.lib)
                 # graph kernel nodes hold their arguments by value: graphs captured so far carry the old anchors
                 self._graph = False
-                self._graph_gen = getattr(self, "_graph_gen", 0) + 1
+                self._graph_gen += 1
 
     def _add_sppf_front(self, op):
         """SPPF.cv1 + the three max pools as one launch (y5_sppf_cv1_pool_fwd); the filter is packed like any conv's and re-packed by refresh_weights()."""
@@ -969,32 +1020,19 @@ class Engine:
         out = nxt["y"]
         args = (self._ptr(y2), self._ld(y2), C.c_void_p(self.be.ptr(wp3)), C.c_void_p(self.be.ptr(bp3)), Kpad3, nxt["c2_store"], 1 if nxt["act"] else 0,
                 self._ptr(out), self._ld(out))
-        lib, st = self.lib, self._stream()
-        fused = C.c_void_p(lib.y5_plan_create())
-        try:
-            if lib.y5_plan_add_bottleneck_cv3(fused, *base, *args, *tail) != 0:
+        lib = self.lib
+        ms_f = self._time_scratch_plan([(lib.y5_plan_add_bottleneck_cv3, (*base, *args, *tail))], 1 if mode == "1" else 10, refusal_ok=True)
+        if ms_f is None:
+            return None
+        if mode != "1":
+            (H3, W3, C13, ldx3, *_r) = _g
+            d3 = _lib.ConvDesc(dtype=self.dt, B=self.spec.B, H=H3, W=W3, C1=C13, ldx=ldx3, OH=out.H, OW=out.W, C2=nxt["c2_store"], ldy=self._ld(out), KH=1, KW=1,
+                               SH=1, SW=1, PH=0, PW=0, act=1 if nxt["act"] else 0, Kpad=Kpad3, Npad=Npad3, ldr=0, ld2=0, cfg=-1, max_blocks=0, split_n=0)
+            ptrs3 = (self._ptr(cat), args[2], args[3], None, self._ptr(out), None)
+            d3.cfg = self._autotune_conv(d3, ptrs3, exclude=SK_CFGS)
+            ms_t = self._time_scratch_plan([(lib.y5_plan_add_bottleneck, (*base, self._ptr(y), self._ld(y), *tail)), (lib.y5_plan_add_conv, (C.byref(d3), *ptrs3))], 10)
+            if not ms_f < ms_t:
                 return None
-            ms_f = C.c_float(0)
-            if lib.y5_plan_time_range(fused, 0, 1, 1 if mode == "1" else 10, st, C.byref(ms_f)) != 0:
-                return None
-            if mode != "1":
-                (H3, W3, C13, ldx3, *_r) = _g
-                d3 = _lib.ConvDesc(dtype=self.dt, B=self.spec.B, H=H3, W=W3, C1=C13, ldx=ldx3, OH=out.H, OW=out.W, C2=nxt["c2_store"], ldy=self._ld(out), KH=1, KW=1,
-                                   SH=1, SW=1, PH=0, PW=0, act=1 if nxt["act"] else 0, Kpad=Kpad3, Npad=Npad3, ldr=0, ld2=0, cfg=-1, max_blocks=0, split_n=0)
-                ptrs3 = (self._ptr(cat), args[2], args[3], None, self._ptr(out), None)
-                d3.cfg = self._autotune_conv(d3, ptrs3, exclude=SK_CFGS)
-                two = C.c_void_p(lib.y5_plan_create())
-                try:
-                    _lib.check(lib.y5_plan_add_bottleneck(two, *base, self._ptr(y), self._ld(y), *tail), lib)
-                    _lib.check(lib.y5_plan_add_conv(two, C.byref(d3), *ptrs3), lib)
-                    ms_t = C.c_float(0)
-                    _lib.check(lib.y5_plan_time_range(two, 0, 2, 10, st, C.byref(ms_t)), lib)
-                finally:
-                    lib.y5_plan_destroy(two)
-                if not ms_f.value < ms_t.value:
-                    return None
-        finally:
-            lib.y5_plan_destroy(fused)
         self._keep += [wp3, bp3]
         self._conv_bufs.append((nxt, wp3, bp3, None, None))
         return dict(args=args, name=nxt["name"])
@@ -1093,31 +1131,17 @@ class Engine:
         y1, y2 = nxt["y"], nxt["y2"]
         args = (C.c_void_p(self.be.ptr(wp2)), C.c_void_p(self.be.ptr(bp2)), c3, Npad2, Kpad2, 1 if nxt["act"] else 0, self._ptr(y1), self._ld(y1),
                 self._ptr(y2), self._ld(y2) if y2 is not None else 0, split)
-        lib, st = self.lib, self._stream()
+        lib = self.lib
         d3 = _lib.ConvDesc.from_buffer_copy(d)
-        best_cfg, ms_f = None, C.c_float(0)
-        kkey = (_K3PW_MARK, int(d.dtype), int(d.B), int(d.H), int(d.W), int(d.ldx), int(c3))   # (the race between the two builds is kept like any other)
-        _load_tune_cache()
-        known = _TUNE_CACHE.get(kkey)
-        for cand in ((known[0],) if known is not None and known[0] in (34, 81) else (34, 81)):  # four waves with two stages each / eight waves with one stage each
-            d3.cfg = cand
-            fused = C.c_void_p(lib.y5_plan_create())
-            try:
-                if lib.y5_plan_add_conv_k3pw(fused, C.byref(d3), ptrs[0], ptrs[1], ptrs[2], *args) != 0:
-                    continue
-                ms = C.c_float(0)
-                if lib.y5_plan_time_range(fused, 0, 1, 1 if (mode == "1" and known is not None) else 10, st, C.byref(ms)) != 0:
-                    continue
-                if best_cfg is None or ms.value < ms_f.value:
-                    best_cfg, ms_f = cand, C.c_float(ms.value)
-            finally:
-                lib.y5_plan_destroy(fused)
-        if best_cfg is None:
+
+        def time_build(cfg, known):
+            d3.cfg = cfg
+            return self._time_scratch_plan([(lib.y5_plan_add_conv_k3pw, (C.byref(d3), *ptrs[:3], *args))], 1 if (mode == "1" and known) else 10, refusal_ok=True)
+
+        # two builds: four waves with two stages each (34) / eight waves with one stage each (81)
+        best = self._pick_build((_K3PW_MARK, int(d.dtype), int(d.B), int(d.H), int(d.W), int(d.ldx), int(c3)), (34, 81), time_build)
+        if best is None:
             return None
-        if known is None:
-            _TUNE_CACHE[kkey] = (best_cfg, -1)
-            _save_tune_cache()
-        d3.cfg = best_cfg
         if mode != "1":
             (H2, W2, C12, ldx2, *_r) = _g
             d2 = _lib.ConvDesc(dtype=self.dt, B=self.spec.B, H=H2, W=W2, C1=C12, ldx=ldx2, OH=y1.H, OW=y1.W, C2=c3, ldy=self._ld(y1), KH=1, KW=1, SH=1, SW=1,
@@ -1125,17 +1149,10 @@ class Engine:
                                max_blocks=0, split_n=nxt.get("split_n", 0))
             ptrs2 = (self._ptr(nxt["x"]), args[0], args[1], None, self._ptr(y1), self._ptr(y2))
             d2.cfg = self._autotune_conv(d2, ptrs2, exclude=SK_CFGS)
-            two = C.c_void_p(lib.y5_plan_create())
-            try:
-                _lib.check(lib.y5_plan_add_conv(two, C.byref(d), *ptrs), lib)
-                _lib.check(lib.y5_plan_add_conv(two, C.byref(d2), *ptrs2), lib)
-                ms_t = C.c_float(0)
-                _lib.check(lib.y5_plan_time_range(two, 0, 2, 10, st, C.byref(ms_t)), lib)
-            finally:
-                lib.y5_plan_destroy(two)
-            if not ms_f.value < ms_t.value:
+            ms_t = self._time_scratch_plan([(lib.y5_plan_add_conv, (C.byref(d), *ptrs)), (lib.y5_plan_add_conv, (C.byref(d2), *ptrs2))], 10)
+            if not best[1] < ms_t:
                 return None
-        d.cfg = d3.cfg
+        d.cfg = best[0]
         self._keep += [wp2, bp2]
         self._conv_bufs.append((nxt, wp2, bp2, None, None))
         # what the fused backbone front (stem + this 3x3 + this 1x1 in one launch, _add_front) needs beside the stem's arguments
@@ -1158,27 +1175,21 @@ class Engine:
         if fa["x_is_stem"].buf != sy.buf or sc2 != 32 or snpad != 32:
             return
         lib, st = self.lib, self._stream()
-        w2, b2, c3, npad2, kpad2, act2, y, ldy, y2, ld2, split = fa["tail"]
-        args = (None, B, H, W, C.c_void_p(self.be.ptr(swp)), C.c_void_p(self.be.ptr(sbp)), sc2, fa["w1"], fa["b1"], fa["C1"], fa["Npad1"], fa["Kpad1"], fa["act1"],
-                w2, b2, c3, npad2, kpad2, act2, y, ldy, y2, ld2, split)
+        args = (B, H, W, C.c_void_p(self.be.ptr(swp)), C.c_void_p(self.be.ptr(sbp)), sc2, fa["w1"], fa["b1"], fa["C1"], fa["Npad1"], fa["Kpad1"], fa["act1"], *fa["tail"])
         if mode != "1":
             # race on the real buffers: a scratch input of the plan's shape stands in for the caller's batch
-            xs = self.be.empty((B, 3, H, W), torch.float16)
-            tmp = C.c_void_p(lib.y5_plan_create())
-            try:
-                if lib.y5_plan_add_conv_front(tmp, C.c_void_p(self.be.ptr(xs)), *args[1:]) != 0:
-                    return
-                ms_f, ms_s, ms_k = C.c_float(0), C.c_float(0), C.c_float(0)
-                if lib.y5_plan_time_range(tmp, 0, 1, 10, st, C.byref(ms_f)) != 0:
-                    return
-                _lib.check(lib.y5_plan_set_input(self.plan, self._stem, C.c_void_p(self.be.ptr(xs))), lib)
-                _lib.check(lib.y5_plan_time_range(self.plan, self._stem, self._stem + 1, 10, st, C.byref(ms_s)), lib)
-                _lib.check(lib.y5_plan_time_range(self.plan, 2, 3, 10, st, C.byref(ms_k)), lib)
-            finally:
-                lib.y5_plan_destroy(tmp)
-            if not ms_f.value < ms_s.value + ms_k.value:
+            scratch = self.be.empty((B, 3, H, W), torch.float16)
+            xs = C.c_void_p(self.be.ptr(scratch))
+            ms_f = self._time_scratch_plan([(lib.y5_plan_add_conv_front, (xs, *args))], 10, refusal_ok=True)
+            if ms_f is None:
                 return
-        if lib.y5_plan_add_conv_front(self.plan, *args) != 0:
+            ms_s, ms_k = C.c_float(0), C.c_float(0)   # its opponents are two ops of this plan: the stem and the 3x3 + pointwise launch
+            _lib.check(lib.y5_plan_set_input(self.plan, self._stem, xs), lib)
+            _lib.check(lib.y5_plan_time_range(self.plan, self._stem, self._stem + 1, 10, st, C.byref(ms_s)), lib)
+            _lib.check(lib.y5_plan_time_range(self.plan, 2, 3, 10, st, C.byref(ms_k)), lib)
+            if not ms_f < ms_s.value + ms_k.value:
+                return
+        if lib.y5_plan_add_conv_front(self.plan, None, *args) != 0:
             return  # shape outside the kernel's range: the two-launch form stays
         self._front = lib.y5_plan_size(self.plan) - 1
         self.op_names.append("front:0.Conv+" + fa["name"])
@@ -1202,46 +1213,27 @@ class Engine:
         arr = (C.c_float * 6)(*apx)
         zp = C.c_void_p(self.be.ptr(self.outputs["z"]))
         args = (dec["ny"], dec["nx"], self.stride_t[lvl], arr, zp, dec["nrows"], dec["row_off"])
-        lib, st = self.lib, self._stream()
-        # two builds of the fused kernel: four waves x two stages (cfg 56) and eight waves x one stage (cfg 87); timed, faster kept
-        # (the choice between the two is kept in the tile-choice cache like any other race: timed once per shape, the same in every later plan)
-        best, tuned = None, int(d.cfg)
-        hkey = (_HEAD_MARK, int(d.dtype), int(d.B), int(d.H), int(d.W), int(d.C1), int(d.C2), int(d.ldx))
-        _load_tune_cache()
-        known = _TUNE_CACHE.get(hkey)
-        for hc in ((known[0],) if known is not None and known[0] in (56, 87) else (56, 87)):
-            d.cfg = hc
-            one = C.c_void_p(lib.y5_plan_create())
-            try:
-                ms_h = C.c_float(0)
-                if (lib.y5_plan_add_detect_head(one, C.byref(d), ptrs[0], ptrs[1], ptrs[2], *args) == 0
-                        and lib.y5_plan_time_range(one, 0, 1, 1 if (mode == "1" and known is not None) else 10, st, C.byref(ms_h)) == 0
-                        and (best is None or ms_h.value < best[0])):
-                    best = (ms_h.value, hc)
-            finally:
-                lib.y5_plan_destroy(one)
-        d.cfg = tuned
+        lib = self.lib
+        dh = _lib.ConvDesc.from_buffer_copy(d)
+
+        def time_build(cfg, known):
+            dh.cfg = cfg
+            return self._time_scratch_plan([(lib.y5_plan_add_detect_head, (C.byref(dh), *ptrs[:3], *args))], 1 if (mode == "1" and known) else 10, refusal_ok=True)
+
+        # two builds of the fused kernel: four waves x two stages (cfg 56) and eight waves x one stage (cfg 87)
+        best = self._pick_build((_HEAD_MARK, int(d.dtype), int(d.B), int(d.H), int(d.W), int(d.C1), int(d.C2), int(d.ldx)), (56, 87), time_build)
         if best is None:
             return None  # shape not supported by the fused kernel
-        if known is None:
-            _TUNE_CACHE[hkey] = (best[1], -1)
-            _save_tune_cache()
         if mode != "1":
-            two = C.c_void_p(lib.y5_plan_create())
-            try:
-                x = dec["x"]
-                _lib.check(lib.y5_plan_add_conv(two, C.byref(d), *ptrs), lib)
-                _lib.check(lib.y5_plan_add_detect_decode(two, self._ptr(x), self.dt, self.spec.B, dec["ny"], dec["nx"], 3, 85, 0, self._ld(x),
-                                                         self.stride_t[lvl], arr, zp, self.dt, dec["nrows"], dec["row_off"], None), lib)
-                ms_t = C.c_float(0)
-                _lib.check(lib.y5_plan_time_range(two, 0, 2, 10, st, C.byref(ms_t)), lib)
-            finally:
-                lib.y5_plan_destroy(two)
-            if not best[0] < ms_t.value:
+            x = dec["x"]
+            decode = (self._ptr(x), self.dt, self.spec.B, dec["ny"], dec["nx"], 3, 85, 0, self._ld(x), self.stride_t[lvl], arr, zp, self.dt, dec["nrows"],
+                      dec["row_off"], None)
+            ms_t = self._time_scratch_plan([(lib.y5_plan_add_conv, (C.byref(d), *ptrs)), (lib.y5_plan_add_detect_decode, decode)], 10)
+            if not best[1] < ms_t:
                 return None
-        d.cfg = best[1]
+        d.cfg = best[0]
         self._keep.append(arr)
-        return dict(level=lvl, args=args, cfg=best[1])
+        return dict(level=lvl, args=args, cfg=best[0])
 
     def _autotune_conv(self, d, ptrs, exclude=()):
         _ensure_sk_workspace(self.be, self.lib, self._stream())
@@ -1262,36 +1254,33 @@ class Engine:
         n = self.lib.y5_plan_size(self.plan)
         if self.fresh_outputs or outputs is not None:
             self._rebind_fresh(n, outputs)
-        if self._stem is not None and src_dt == _lib.Y5_F16:
-            # fp16 NCHW batch: the stem conv reads it in place (no NHWC repack pass), then the plan continues at op 2 -- or, with the fused
-            # front (stem + 1.Conv + 2.C3.cv1+cv2 in one launch), at op 4
-            self._stem_active = True
-            head = self._front if self._front is not None else self._stem
-            body0 = 4 if self._front is not None else 2
+        self._stem_active = self._stem is not None and src_dt == _lib.Y5_F16
+        if self._stem_active:
+            (head, _), (body0, body1) = self._plan_ranges(True)
             _lib.check(self.lib.y5_plan_set_input(self.plan, head, C.c_void_p(xptr)), self.lib)
             _lib.check(self.lib.y5_plan_run_range(self.plan, head, head + 1, st), self.lib)
             if self._insitu and not self._graph:
-                self._refine_in_situ(body0, self._stem)
+                self._refine_in_situ(body0, body1)
             if self._use_graph:
                 # the body only touches plan-owned buffers and the bound outputs: replayed as ONE hipGraph launch (captured on first
                 # use of every output binding)
                 if not self._graph:
-                    if self.lib.y5_plan_capture_range(self.plan, body0, self._stem, st) == 0:
+                    if self.lib.y5_plan_capture_range(self.plan, body0, body1, st) == 0:
                         self._graph = True
                     else:  # capture refused by the runtime: same kernels, launched one by one
                         self._use_graph = False
             if self._use_graph:
                 _lib.check(self.lib.y5_plan_launch_graph(self.plan, st), self.lib)
             else:
-                _lib.check(self.lib.y5_plan_run_range(self.plan, body0, self._stem, st), self.lib)
+                _lib.check(self.lib.y5_plan_run_range(self.plan, body0, body1, st), self.lib)
             return self._tag_hint()
-        self._stem_active = False
+        ((lo, hi),) = self._plan_ranges(False)
         scale = 1.0 / 255.0 if src_dt == _lib.Y5_U8 else 1.0  # train.py:379 / detect.py:209: uint8 images -> 0..1
         _lib.check(self.lib.y5_nchw_to_nhwc(C.c_void_p(xptr), src_dt, self._ptr(d), self.dt, B, cin, d.H, d.W, self._ld(d),
                                             scale, st), self.lib)
         if self._insitu:
-            self._refine_in_situ(1, n if self._stem is None else self._stem)
-        _lib.check(self.lib.y5_plan_run_range(self.plan, 1, n if self._stem is None else self._stem, st), self.lib)
+            self._refine_in_situ(lo, hi)
+        _lib.check(self.lib.y5_plan_run_range(self.plan, lo, hi, st), self.lib)
         return self._tag_hint()
 
     def _tag_hint(self):
@@ -1332,7 +1321,7 @@ class Engine:
                 self._bound[name] = new
                 changed = True
         if changed or not self._graph:
-            key = hash((getattr(self, "_graph_gen", 0),) + tuple(sorted(self._bound.items()))) & 0xFFFFFFFFFFFFFFFF
+            key = hash((self._graph_gen,) + tuple(sorted(self._bound.items()))) & 0xFFFFFFFFFFFFFFFF
             self._graph = self.lib.y5_plan_select_graph(self.plan, key) == 1
 
     def _refine_in_situ(self, lo, hi):
@@ -1425,13 +1414,8 @@ class Engine:
         """In-situ per-op HIP-event timing: [(name, ms)] in execution order, every op timed in its real position of one eager
         forward (median of `iters` passes) -- what bench.py's roofline is computed from.  Call after at least one forward."""
         st = self._stream()
-        n = self.lib.y5_plan_size(self.plan)
         res = []
-        if self._stem is not None and getattr(self, "_stem_active", False):
-            ranges = [(self._front, self._front + 1), (4, self._stem)] if self._front is not None else [(self._stem, self._stem + 1), (2, self._stem)]
-        else:
-            ranges = [(1, n if self._stem is None else self._stem)]
-        for lo, hi in ranges:
+        for lo, hi in self._plan_ranges(self._stem_active):
             buf = (C.c_float * (hi - lo))()
             _lib.check(self.lib.y5_plan_profile_range(self.plan, lo, hi, iters, st, buf), self.lib)
             res += [(self.op_names[lo + k], float(buf[k])) for k in range(hi - lo)]
@@ -1440,14 +1424,9 @@ class Engine:
     def time_ops(self, iters=20):
         """Per-op HIP-event timing (ms per launch) on the current stream: [(name, ms)] -- used by bench.py."""
         st = self._stream()
-        n = self.lib.y5_plan_size(self.plan)
         res = []
         ms = C.c_float(0)
-        if self._stem is not None and getattr(self, "_stem_active", False):
-            # as executed by __call__ for an fp16 batch
-            order = [self._front] + list(range(4, self._stem)) if self._front is not None else [self._stem] + list(range(2, self._stem))
-        else:
-            order = list(range(1, n if self._stem is None else self._stem))
+        order = [i for lo, hi in self._plan_ranges(self._stem_active) for i in range(lo, hi)]   # as executed by the latest forward
         for i in order:
             _lib.check(self.lib.y5_plan_time_range(self.plan, i, i + 1, iters, st, C.byref(ms)), self.lib)
             res.append((self.op_names[i], ms.value / iters))
