@@ -413,6 +413,21 @@ int y5_process_mask(const void* protos, int proto_dtype, int c, int mh, int mw, 
 typedef struct y5_mask_img { const float* masks_in; const float* boxes; int ld_m, ld_b, n; } y5_mask_img;
 int y5_process_mask_batch(const void* protos, int proto_dtype, int B, int c, int mh, int mw, const y5_mask_img* imgs, int ih, int iw, int upsample,
                           void* out, int out_dtype, void* stream);
+/* Masks in the pixels of the ORIGINAL images -- utils/segment/general.py:54-76 `process_mask_native`, the `retina_masks` branch of
+ * segment/predict.py:167-170 -- for a whole batch in one launch, every image with its own size.  protos (B, c, mh, mw) f16|f32; image b has
+ * imgs[b].n instances with coefficient rows at masks_in + i*ld_m and xyxy boxes in ORIGINAL-image pixels at boxes + i*ld_b (read as given:
+ * the caller has run scale_boxes and .round() on them, predict.py:169).  top / left / ch / cw: the window of the prototype plane that is left
+ * after the letterbox padding is cut away, rows [top, top + ch) and columns [left, left + cw), computed by the caller as general.py:68-71 does
+ * (two different int() truncations; an empty window is Y5_ERR_BAD_ARG).  The uncropped sigmoid plane of that window is resized to (h0, w0)
+ * with upsample_bilinear2d's fp32 arithmetic (align_corners=False, taps clamped at the WINDOW's edge, scale above or below 1), pixel (X, Y)
+ * is kept where x1 <= X < x2 and y1 <= Y < y2, then > 0.5.  out: one buffer of out_elems elements, 16-byte aligned; image b's (n, h0, w0)
+ * block starts at element out_off, a multiple of 16 bytes; element type Y5_F32 (0.f / 1.f) or Y5_U8.  Nothing outside the blocks is written.
+ * `imgs` is a HOST array, copied into the kernel arguments (48 images per launch); images with n == 0 and an all-empty batch launch nothing. */
+typedef struct y5_mask_native_img {
+  const float* masks_in; const float* boxes; int ld_m, ld_b, n, h0, w0, top, left, ch, cw; long long out_off;
+} y5_mask_native_img;
+int y5_process_mask_native_batch(const void* protos, int proto_dtype, int B, int c, int mh, int mw, const y5_mask_native_img* imgs, void* out,
+                                 long long out_elems, int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * y5_letterbox_batch -- the image pre-processing chain for a batch in one launch:

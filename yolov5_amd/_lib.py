@@ -38,6 +38,13 @@ class MaskImg(C.Structure):
     _fields_ = [("masks_in", C.c_void_p), ("boxes", C.c_void_p), ("ld_m", C.c_int), ("ld_b", C.c_int), ("n", C.c_int)]
 
 
+class MaskNativeImg(C.Structure):
+    """y5_mask_native_img (include/yolov5_hip.h): one image of y5_process_mask_native_batch."""
+
+    _fields_ = [("masks_in", C.c_void_p), ("boxes", C.c_void_p), ("ld_m", C.c_int), ("ld_b", C.c_int), ("n", C.c_int), ("h0", C.c_int),
+                ("w0", C.c_int), ("top", C.c_int), ("left", C.c_int), ("ch", C.c_int), ("cw", C.c_int), ("out_off", C.c_longlong)]
+
+
 class ConvDesc(C.Structure):
     """y5_conv_desc (include/yolov5_hip.h)."""
 
@@ -191,6 +198,8 @@ EXPORTS = {
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "y5_process_mask_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MaskImg), C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_int, C.c_void_p]),
+    "y5_process_mask_native_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MaskNativeImg), C.c_void_p,
+                                               C.c_longlong, C.c_int, C.c_void_p]),
     "y5_mosaic_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "y5_polygon_masks_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "y5_polygon_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

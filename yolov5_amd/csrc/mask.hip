@@ -319,3 +319,4 @@ extern "C" int y5_process_mask(const void* protos, int proto_dtype, int c, int m
   return y5_check_launch("y5_process_mask");
 }
 #include "seg_val.h"   // y5_val_match_masks: the mask branch of validation matching (same flags as the mask kernels above)
+#include "mask_native.h"   // y5_process_mask_native_batch: masks at each image's own resolution (same flags, same mask_value.h)

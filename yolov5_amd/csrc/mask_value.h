@@ -27,3 +27,22 @@ __device__ __forceinline__ float y5_mask_lowres(const TP* P, long long plane, in
   }
   return v;
 }
+
+// The same value WITHOUT the crop, for process_mask_native (utils/segment/general.py:67): there the sigmoid plane is resized first and
+// crop_mask runs at full resolution (:74-75), so every pixel of the window carries sigmoid(coef . protos[:, gy, gx]).  The order of the
+// additions, the 8-wide unroll and 1 / (1 + expf(-s)) are y5_mask_lowres's.
+template <typename TP>
+__device__ __forceinline__ float y5_mask_value(const TP* P, long long plane, int mw, int c, const float* coef, int gx, int gy) {
+  float s = 0.f;
+  const TP* q = P + (long long)gy * mw + gx;
+  int k = 0;
+  for (; k + 8 <= c; k += 8) {
+    TP t[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t[e] = q[(k + e) * plane];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += coef[k + e] * (float)t[e];
+  }
+  for (; k < c; ++k) s += coef[k] * (float)q[k * plane];
+  return 1.0f / (1.0f + expf(-s));
+}
