@@ -450,6 +450,43 @@ int y5_letterbox_batch(const y5_letterbox_job* jobs_dev, int B, int H, int W, in
                        int dst_chw, int div255, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Classification (models/common.py:1120-1140 Classify, utils/augmentations.py:297-341 classify_transforms,
+ * classify/predict.py:120-153, classify/val.py:104-147).  Inference only.
+ *
+ * y5_classify_transform_batch -- classify_transforms(S) for a ragged batch of u8 HWC BGR frames in one launch: centre crop of
+ *   m = min(h0, w0) pixels at top = (h0 - m) / 2, left = (w0 - m) / 2, cv2.resize(crop, (S, S), INTER_LINEAR) (the restated 8-bit
+ *   algorithm of y5_letterbox_batch: parity-unpinned), BGR -> RGB, then dst[b, c, y, x] = lut[c * 256 + pixel]: the caller's
+ *   3 x 256 fp32 table holds ToTensor + Normalize, ((u / 255) - mean[c]) / std[c] in fp32, c in RGB order.  jobs_dev: DEVICE array
+ *   of B jobs (`stride` bytes per source row, >= 3 * w0; a job that breaks this leaves its image unwritten).  dst: (B, 3, S, S)
+ *   Y5_F32 or Y5_F16 (the fp32 value rounded to nearest even), 16-byte aligned.
+ *
+ * y5_classify_head -- average pool + Linear behind the Classify convolution.  x: the convolution's NHWC output (B, HW, C), `ld`
+ *   elements per pixel, Y5_F16 | Y5_F32; w: (nc, C) row-major in the same dtype; bias: (nc) fp32; logits: (B, nc) in the same dtype,
+ *   `ldo` elements per row.  pooled[b, c] = (fp32 sum over the pixels) / HW stays fp32; logits[b, j] = bias[j] + sum_c pooled * w in
+ *   fp32.  Every (b, j) is summed in an order that depends on (HW, C) only: a batch equals its single-row calls bit for bit.
+ *   form: 1 = one launch (a workgroup per image, no workspace), 2 = pool kernel + GEMM (fp16: MFMA) through a workspace of
+ *   y5_classify_head_workspace_bytes(B, C) bytes, 16-byte aligned (Y5_ERR_WORKSPACE otherwise), 0 = the faster of the two on the
+ *   MI355X (form 2).  Any HW >= 1 and nc >= 1; C % 8 == 0, C <= 8192 and 16-byte aligned pixel rows, else Y5_ERR_UNSUPPORTED.
+ *
+ * y5_classify_post -- what predict.py:133,152 and val.py:119,122 do with a batch of logits, in one launch without a host
+ *   synchronisation.  logits: (B, nc) Y5_F16 | Y5_F32 (widened exactly to fp32), `ld` elements per row.  top5: (B, 5) int32, the first
+ *   min(5, nc) columns of argsort(1, descending=True), unused columns -1; equal values rank by ascending index (the reference's
+ *   unstable sort leaves their order undefined).  probs (optional): (B, nc) fp32 softmax(dim=1).  row_loss (optional, needs labels):
+ *   (B) fp32 nn.CrossEntropyLoss(label_smoothing, reduction='none') = (1 - eps) (lse - z_y) + eps (lse - mean(z)); labels: (B) int32
+ *   (a label outside [0, nc) gives NaN).  labels == NULL: row_loss is not touched.  nc <= 36864, else Y5_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct y5_classify_job {
+  const void* src;
+  int h0, w0, stride, reserved;
+} y5_classify_job;
+int y5_classify_transform_batch(const y5_classify_job* jobs_dev, int B, int S, const float* lut, void* dst, int dst_dtype, void* stream);
+size_t y5_classify_head_workspace_bytes(int B, int C);
+int y5_classify_head(const void* x, int dtype, int B, int HW, int C, int ld, const void* w, const float* bias, int nc, void* logits, int ldo,
+                     int form, void* workspace, size_t workspace_bytes, void* stream);
+int y5_classify_post(const void* logits, int dtype, int B, int nc, int ld, const int* labels, float label_smoothing, int* top5, float* probs,
+                     float* row_loss, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * y5_val_match -- val.py:296-307 for every image of a batch in one launch: de-letterbox the predictions and the labels
  * (`scale_boxes` with ratio_pad, utils/general.py:613-626) and `process_batch` (utils/metrics.py:224-265, box branch;
  * `box_iou` of ultralytics.utils.metrics, call site utils/metrics.py:252).
@@ -635,6 +672,8 @@ int y5_plan_set_obj_hint(y5_plan*, int op_index, void* obj_hint);  /* Detect dec
 int y5_plan_add_bottleneck_cv3(y5_plan*, const void* x, int ldx, const void* w1_packed, const float* bias1, int Kpad1, const void* w2_packed,
                                const float* bias2, int Kpad2, const void* y2, int ld2, const void* w3_packed, const float* bias3, int Kpad3, int C3,
                                int act3, void* out, int ldo, int B, int H, int W, int C, int add);
+int y5_plan_add_classify_head(y5_plan*, const void* x, int dtype, int B, int HW, int C, int ld, const void* w, const float* bias, int nc,
+                              void* logits, int ldo, int form, void* workspace, size_t workspace_bytes);
 int y5_plan_add_nop(y5_plan*);  /* placeholder op: keeps the op numbering of the conv + decode form next to a fused head */
 int y5_plan_add_conv_stem(y5_plan*, const void* x_nchw, int B, int H, int W, const void* w_stem, const float* bias, int C2,
                           int Npad, void* y, int ldy);

@@ -82,6 +82,11 @@ class LetterboxJob(C.Structure):
     _fields_ = [("src", C.c_void_p)] + [(n, C.c_int) for n in ("h0", "w0", "stride", "nw", "nh", "top", "left")]
 
 
+class ClassifyJob(C.Structure):
+    """include/yolov5_hip.h: y5_classify_job (one image of a y5_classify_transform_batch launch)."""
+    _fields_ = [("src", C.c_void_p)] + [(n, C.c_int) for n in ("h0", "w0", "stride", "reserved")]
+
+
 class MosaicJob(C.Structure):
     """include/yolov5_hip.h: y5_mosaic_job (one output image of a y5_mosaic_batch launch)."""
     _fields_ = [("src", C.c_void_p * 4)] + [(n, C.c_int * 4) for n in ("h0", "w0", "stride", "rh", "rw", "x1a", "y1a", "x2a", "y2a", "x1b", "y1b")] + \
@@ -205,6 +210,13 @@ EXPORTS = {
     "y5_polygon_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_letterbox_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "y5_classify_transform_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "y5_classify_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "y5_classify_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "y5_classify_post": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y5_plan_add_classify_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "y5_val_match": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "y5_val_match_masks_ws_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),

@@ -101,3 +101,101 @@ def letterbox_batch(ims, new_shape=(640, 640), color=(114, 114, 114), auto=False
     _launch(ims, geos, H, W, _pad_value(color), swap_rb, out, True, normalize and dtype != torch.uint8)
     shapes = [((im.shape[0], im.shape[1]), (g["ratio"], g["pad"])) for im, g in zip(ims, geos)]
     return out, shapes
+
+
+# ---- classification transforms (utils/augmentations.py:15-16, 297-341) ------------------------------------------------------------------------
+IMAGENET_MEAN = 0.485, 0.456, 0.406  # RGB mean
+IMAGENET_STD = 0.229, 0.224, 0.225  # RGB standard deviation
+
+_CLS_LUT = {}  # (device, mean, std) -> (3, 256) fp32 table of ToTensor + Normalize
+
+
+def _classify_lut(device, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """lut[c][u] = ((u / 255) - mean[c]) / std[c] with the reference's own two fp32 expressions: ToTensor's `im.float(); im /= 255.0`
+    (utils/augmentations.py:339-340) and Normalize's `sub(mean).div(std)` with fp32 mean / std.  c in RGB order.  Host arithmetic, once per device."""
+    key = (str(device), tuple(mean), tuple(std))
+    if key not in _CLS_LUT:
+        u = torch.arange(256, dtype=torch.uint8).float()
+        u /= 255.0
+        t = u.expand(3, 256).clone().sub_(torch.tensor(mean, dtype=torch.float32).view(3, 1)).div_(torch.tensor(std, dtype=torch.float32).view(3, 1))
+        _CLS_LUT[key] = t.contiguous().to(device)
+    return _CLS_LUT[key]
+
+
+def _as_device_image(im, device):
+    if not torch.is_tensor(im):  # host array: only its bytes cross the bus
+        import numpy as np
+
+        im = torch.from_numpy(np.ascontiguousarray(im)).to(device)
+    return _check_image(im)
+
+
+def classify_transform_batch(ims, size=224, half=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
+    """classify_transforms(size) for a ragged batch of uint8 HWC BGR images in ONE launch (csrc/classify_data.h, y5_classify_transform_batch):
+    centre crop through cv2.resize, BGR -> RGB, / 255, ImageNet normalise -> (B, 3, size, size) fp32, or fp16 (`im.half()`, classify/predict.py:123)."""
+    assert isinstance(size, int), f"ERROR: classify_transforms size {size} must be integer, not (list, tuple)"
+    if not len(ims):
+        raise ValueError("classify_transforms: empty batch")
+    if device is None:
+        device = next((im.device for im in ims if torch.is_tensor(im)), None)
+        if device is None:
+            raise ValueError("classify_transforms: host arrays need a device=")
+    ims = [_as_device_image(im, device) for im in ims]
+    dev = ims[0].device
+    jobs = (_lib.ClassifyJob * len(ims))()
+    for j, im in zip(jobs, ims):
+        j.src, j.h0, j.w0, j.stride = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
+    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev, non_blocking=False)
+    out = torch.empty((len(ims), 3, size, size), dtype=torch.float16 if half else torch.float32, device=dev)
+    lib = _lib.lib()
+    rc = lib.y5_classify_transform_batch(C.c_void_p(table.data_ptr()), len(ims), size, C.c_void_p(_classify_lut(dev, mean, std).data_ptr()),
+                                         C.c_void_p(out.data_ptr()), _lib.Y5_F16 if half else _lib.Y5_F32, _lib.stream(dev))
+    _lib.check(rc, lib)
+    return out
+
+
+class CenterCrop:
+    """utils/augmentations.py:304-320 on a device uint8 HWC image: the centre square resized to `size` (uint8 HWC, the resize kernel of letterbox)."""
+
+    def __init__(self, size=640):
+        self.h, self.w = (size, size) if isinstance(size, int) else size
+
+    def __call__(self, im):
+        im = _check_image(im)
+        imh, imw = im.shape[:2]
+        m = min(imh, imw)
+        top, left = (imh - m) // 2, (imw - m) // 2
+        out = torch.empty((1, self.h, self.w, 3), dtype=torch.uint8, device=im.device)
+        geo = dict(new_unpad=(self.w, self.h), top=0, left=0)
+        _launch([im[top:top + m, left:left + m]], [geo], self.h, self.w, 0, False, out, False, False)
+        return out[0]
+
+
+class ToTensor:
+    """utils/augmentations.py:323-341 on a device uint8 HWC BGR image: RGB CHW, fp32 (or fp16), / 255 -- one launch of the letterbox kernel without
+    a resize.  (fp16: the kernel divides the exactly widened value in fp32 and rounds once, as `.half() / 255` does on the device.)"""
+
+    def __init__(self, half=False):
+        self.half = half
+
+    def __call__(self, im):
+        im = _check_image(im)
+        h, w = im.shape[:2]
+        out = torch.empty((1, 3, h, w), dtype=torch.float16 if self.half else torch.float32, device=im.device)
+        _launch([im], [dict(new_unpad=(w, h), top=0, left=0)], h, w, 0, True, out, True, True)
+        return out[0]
+
+
+class _ClassifyTransforms:
+    def __init__(self, size):
+        self.size = size
+
+    def __call__(self, ims, half=False, device=None):
+        return classify_transform_batch(ims if isinstance(ims, (list, tuple)) else [ims], self.size, half=half, device=device)
+
+
+def classify_transforms(size=224):
+    """utils/augmentations.py:297-301: Compose([CenterCrop(size), ToTensor(), Normalize(IMAGENET_MEAN, IMAGENET_STD)]) -- here one callable that takes
+    the whole (ragged) list of uint8 HWC BGR images and returns the (B, 3, size, size) batch from one launch."""
+    assert isinstance(size, int), f"ERROR: classify_transforms size {size} must be integer, not (list, tuple)"
+    return _ClassifyTransforms(size)

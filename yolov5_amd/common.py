@@ -3,7 +3,7 @@ that YAML configs, `state_dict`s and pickled checkpoints of the reference map 1:
 hand-written HIP kernels through yolov5_amd.engine (no torch ops, no CPU path).
 
 Covered: autopad :62, Conv :74-92, Bottleneck :164-181, C3 :230-246, SPPF :318-340, Concat :443-453,
-Proto :1104-1117, DetectMultiBackend (pt branch) :456-814, AutoShape :843-948, Detections (tensor part) :950-1101.
+Proto :1104-1117, Classify :1120-1140, DetectMultiBackend (pt branch) :456-814, AutoShape :843-948, Detections (tensor part) :950-1101.
 """
 from __future__ import annotations
 
@@ -123,6 +123,27 @@ class Proto(_HipModule):
         return self._run_single(x, "proto")
 
 
+class Classify(nn.Module):
+    """Classification head (models/common.py:1120-1140): Conv to 1280 channels, global average pool, Dropout, Linear.  Inside a
+    ClassificationModel the Conv is an ordinary plan convolution and pool + Linear are one y5_classify_head op (csrc/classify.h); Dropout is
+    the identity in eval mode, the only mode built.  Attribute names and state-dict keys are the reference's."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1, dropout_p=0.0):
+        super().__init__()
+        if g != 1:
+            raise NotImplementedError("yolov5_amd.Classify: grouped convolutions are outside the hot path")
+        c_ = 1280  # efficientnet_b0 size
+        self.conv = Conv(c1, c_, k, s, autopad(k, p), g)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.drop = nn.Dropout(p=dropout_p, inplace=True)
+        self.linear = nn.Linear(c_, c2)
+
+    def forward(self, x):
+        if isinstance(x, list):
+            raise NotImplementedError("yolov5_amd.Classify: a list input (the torch.cat branch of models/common.py:1138-1139) is not built")
+        raise RuntimeError("yolov5_amd.Classify is executed by the model engine; call the parent ClassificationModel")
+
+
 # ----------------------------------------------------------------------------------------------------------
 class DetectMultiBackend(nn.Module):
     """Backend selector of the reference (models/common.py:456-814) reduced to its PyTorch (`pt`) branch
@@ -150,7 +171,9 @@ class DetectMultiBackend(nn.Module):
         model.half() if fp16 else model.float()
         self.model = model
         self.stride = max(int(model.stride.max()), 32)
-        self.names = model.module.names if hasattr(model, "module") else model.names
+        inner = model.module if hasattr(model, "module") else model
+        # (a ClassificationModel cut from a detection model carries no names: the reference's default, models/common.py:679)
+        self.names = inner.names if hasattr(inner, "names") else {i: f"class{i}" for i in range(999)}
         self.pt, self.jit, self.onnx, self.engine, self.xml, self.triton = True, False, False, False, False, False
         self.fp16 = fp16
         self.device = torch.device(device)

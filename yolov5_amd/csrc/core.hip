@@ -142,6 +142,11 @@ struct SppfFrontArgs {
   template <class F> void outputs(F&& f) { f(buf); }
 };
 
+struct ClassifyHeadArgs {
+  const void* x; int dtype, B, HW, C, ld; const void* w; const float* bias; int nc; void* logits; int ldo, form; void* workspace; size_t workspace_bytes;
+  template <class F> void outputs(F&& f) { f(logits); }
+};
+
 static int run(const ConvArgs& a, void* st) { return y5_conv2d_fwd(&a.d, a.x, a.w_packed, a.bias, a.residual, a.y, a.y_up2, st); }
 static int run(const ToNhwcArgs& a, void* st) { return y5_nchw_to_nhwc(a.src, a.src_dtype, a.dst, a.dst_dtype, a.B, a.C, a.H, a.W, a.ld, a.scale, st); }
 static int run(const ToNchwArgs& a, void* st) { return y5_nhwc_to_nchw(a.src, a.dtype, a.dst, a.B, a.C, a.H, a.W, a.ld, st); }
@@ -175,8 +180,12 @@ static int run(const SppfFrontArgs& a, void* st) {
   return y5_sppf_cv1_pool_fwd(a.x, a.ldx, a.w_packed, a.bias, a.Kpad, a.buf, a.ld, a.B, a.H, a.W, a.C1, a.c_, a.k, a.act, st);
 }
 
+static int run(const ClassifyHeadArgs& a, void* st) {
+  return y5_classify_head(a.x, a.dtype, a.B, a.HW, a.C, a.ld, a.w, a.bias, a.nc, a.logits, a.ldo, a.form, a.workspace, a.workspace_bytes, st);
+}
+
 using OpArgs = std::variant<NopArgs, ConvArgs, ToNhwcArgs, ToNchwArgs, SppfPoolArgs, UpsampleArgs, CopyArgs, DecodeArgs, HeadArgs, StemArgs, BneckArgs, K3pwArgs,
-                            BneckCv3Args, FrontArgs, SppfFrontArgs>;
+                            BneckCv3Args, FrontArgs, SppfFrontArgs, ClassifyHeadArgs>;
 
 struct Op {
   int branch;  // 0: the caller's stream; 1: the plan's side stream (forked after the preceding main op, joined at the end of the range)
@@ -333,6 +342,15 @@ extern "C" int y5_plan_add_conv_front(y5_plan* pl, const void* x_nchw, int B, in
   a.x_nchw = x_nchw; a.B = B; a.H = H; a.W = W; a.w_stem = w_stem; a.bias0 = bias0; a.C0 = C0; a.w1_packed = w1; a.bias1 = bias1; a.C1 = C1; a.Npad1 = Npad1;
   a.Kpad1 = Kpad1; a.act1 = act1; a.w2_packed = w2; a.bias2 = bias2; a.C3 = C3; a.Npad2 = Npad2; a.Kpad2 = Kpad2; a.act2 = act2; a.y = y; a.ldy = ldy;
   a.y2 = y2; a.ld2 = ld2; a.split_n = split_n;
+  return plan_push(pl, a);
+}
+// classification head (head.hip, classify.h): average pool + Linear behind the Classify convolution; `logits` is re-pointed per call like z
+extern "C" int y5_plan_add_classify_head(y5_plan* pl, const void* x, int dtype, int B, int HW, int C, int ld, const void* w, const float* bias, int nc,
+                                         void* logits, int ldo, int form, void* workspace, size_t workspace_bytes) {
+  if (!pl) return y5_fail(Y5_ERR_BAD_ARG, "plan_add_classify_head: null");
+  ClassifyHeadArgs a{};
+  a.x = x; a.dtype = dtype; a.B = B; a.HW = HW; a.C = C; a.ld = ld; a.w = w; a.bias = bias; a.nc = nc; a.logits = logits; a.ldo = ldo; a.form = form;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes;
   return plan_push(pl, a);
 }
 extern "C" int y5_plan_add_nop(y5_plan* pl) {

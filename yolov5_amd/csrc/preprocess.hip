@@ -19,6 +19,7 @@
 #include "y5_common.h"
 #include "y5_host.h"
 #include "resize_u8.h"
+#include "classify_data.h"   // y5_classify_transform_batch: the classification transform (CenterCrop + ToTensor + Normalize)
 
 namespace {
 constexpr int PX = 8;  // output pixels per lane

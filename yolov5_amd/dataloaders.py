@@ -643,3 +643,32 @@ class SegValLoader:
             imgs, targets, shapes, masks = seg_letterbox_batch(self.images, self.labels, self.segments, ids, self.s, self.dtype, normalize=True,
                                                                overlap=self.overlap, mask_ratio=self.mask_ratio)
             yield imgs, targets, [self.paths[i] for i in ids], shapes, masks
+
+
+# ---- classification (utils/dataloaders.py:949-1013, the augment=False branch) -------------------------------------------------------------
+class ClassificationLoader:
+    """`ClassificationDataset.__getitem__`'s torch_transforms branch plus the default collate, on frames already in memory: yields
+    (images (b, 3, imgsz, imgsz) fp32 | fp16, labels (b) int64) on the device, ONE transform launch per batch (augmentations.classify_transform_batch).
+    frames: uint8 HWC BGR images of any sizes (device tensors, or host arrays uploaded per batch); the last batch may be short.  Reading image folders,
+    the RAM / disk caches and the train-time albumentations branch are not built."""
+
+    def __init__(self, frames, labels, imgsz=224, batch_size=64, half=False, device=None):
+        if len(frames) != len(labels):
+            raise ValueError(f"ClassificationLoader: {len(frames)} frames, {len(labels)} labels")
+        self.frames, self.imgsz, self.batch_size, self.half = list(frames), int(imgsz), int(batch_size), half
+        if device is None:
+            device = next((f.device for f in self.frames if torch.is_tensor(f)), None)
+        if device is None:
+            raise ValueError("ClassificationLoader: host frames need a device=")
+        self.device = torch.device(device)
+        self.labels = torch.as_tensor(np.asarray(labels), dtype=torch.int64).to(self.device)
+
+    def __len__(self):
+        return (len(self.frames) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        from .augmentations import classify_transform_batch
+
+        for b0 in range(0, len(self.frames), self.batch_size):
+            ims = self.frames[b0:b0 + self.batch_size]
+            yield classify_transform_batch(ims, self.imgsz, half=self.half, device=self.device), self.labels[b0:b0 + len(ims)]

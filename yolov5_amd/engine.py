@@ -229,7 +229,7 @@ class _Planner:
                 if m.d != 1:
                     raise NotImplementedError("Concat along a dimension other than channels")
                 shp.append((sum(s[0] for s in ins), h, w))
-            elif isinstance(m, yo.Detect):
+            elif isinstance(m, (yo.Detect, cm.Classify)):
                 shp.append(None)
             else:
                 raise NotImplementedError(f"layer {i}: {type(m).__name__} has no HIP implementation")
@@ -328,6 +328,8 @@ class _Planner:
                 out[i] = buf
             elif isinstance(m, yo.Detect):
                 self.detect(m, ins)
+            elif isinstance(m, cm.Classify):
+                self.classify(m, ins, name=f"{i}.Classify")
         # opt-in since round 2: the A/B on MI355X (scripts/ab_head_branch.sh) shows no gain any more, and without overlapping launches the
         # per-kernel durations of a rocprofv3 trace add up to the forward
         if _lib.experimental("head_branch"):
@@ -377,6 +379,16 @@ class _Planner:
                 ops[k]["side"] = True
                 new.append(ops[k])
         self.spec.ops[:] = new
+
+    def classify(self, m, xs, name="Classify"):
+        """Classify (common.py:1120-1140): its Conv is an ordinary convolution op (raced by the tuner like any other); the average pool and the
+        Linear behind it are ONE op (csrc/classify.h) that writes the plan output "logits"."""
+        if len(xs) != 1:
+            raise NotImplementedError("Classify on a list of inputs (the torch.cat branch of models/common.py:1138-1139) is not built")
+        t = self.conv([m.conv], xs[0], None, name=name + ".conv")
+        nc = m.linear.out_features
+        self.spec.ops.append(dict(op="classify_head", x=t, mod=m.linear, nc=nc, name=name + ".pool+linear"))
+        self.spec.outputs["logits"] = dict(shape=(self.spec.B, nc))
 
     def detect(self, m, xs):
         spec = self.spec
@@ -709,6 +721,7 @@ class Engine:
             self.anchors = det.anchors.detach().float().cpu().clone()
         self._keep = []  # device tensors referenced by raw pointers inside the C plan
         self._conv_bufs = []  # (op, packed filter, bias, stem filter, stem bias) of every conv op -> refresh_weights()
+        self._linear_bufs = []  # (nn.Linear, weight in the plan's dtype, fp32 bias) of the classification head -> refresh_weights()
         self.bufs = [self.be.empty((B, b.H, b.W, b.C), dtype) for b in self.spec.bufs]
         # The raw (bs, na, ny, nx, no) head tensors of eval mode (models/yolo.py:96-98) are the Detect convs' NHWC outputs seen
         # through another index order: on the GPU they are returned as strided VIEWS of those plan buffers instead of being
@@ -896,6 +909,8 @@ class Engine:
             if rc == 0 and self._hint:
                 rc = lib.y5_plan_set_obj_hint(self.plan, lib.y5_plan_size(self.plan) - 1, C.c_void_p(self.be.ptr(self._hint_t)))
             self.op_names.append(f"decode{i}")
+        elif kind == "classify_head":
+            rc = self._add_classify_head(op)
         elif kind == "to_nchw":
             s = op["src"]
             o = self.outputs[op["out"]]
@@ -930,6 +945,29 @@ class Engine:
         main = pack_conv_weight(w, b, self.dtype)
         return (H, W, C1, ldx, kh, kw, sh, sw, ph, pw), main, stem
 
+    def _linear_weights(self, lin):
+        """(weight (nc, C) in the plan's dtype, fp32 bias) of the classification head's nn.Linear from the LIVE parameters."""
+        w = lin.weight.detach().to(self.dtype).contiguous()
+        b = torch.zeros(lin.out_features, device=w.device) if lin.bias is None else lin.bias.detach().float().contiguous()
+        return w, b
+
+    def _add_classify_head(self, op):
+        """Average pool + Linear of the Classify head as one plan op (y5_classify_head).  Y5_CLASSIFY_HEAD_FORM = 1 / 2 picks the one-launch /
+        the pool + GEMM form for A/B runs; unset, the library's measured default runs."""
+        x, lin = op["x"], op["mod"]
+        if lin.in_features != x.C:
+            raise ValueError(f"classify head: Linear expects {lin.in_features} channels, the convolution delivers {x.C}")
+        wp, bp = (self.be.from_torch(t) for t in self._linear_weights(lin))
+        nbytes = int(self.lib.y5_classify_head_workspace_bytes(self.spec.B, x.C))
+        ws = self.be.empty((nbytes + 256,), torch.uint8)
+        self._keep += [wp, bp, ws]
+        self._linear_bufs.append((lin, wp, bp))
+        self.op_names.append("classify_head:" + op["name"])
+        wsp = self.be.ptr(ws)
+        return self.lib.y5_plan_add_classify_head(self.plan, self._ptr(x), self.dt, self.spec.B, x.H * x.W, x.C, self._ld(x), C.c_void_p(self.be.ptr(wp)),
+                                                  C.c_void_p(self.be.ptr(bp)), op["nc"], C.c_void_p(self.be.ptr(self.outputs["logits"])), op["nc"],
+                                                  int(os.environ.get("Y5_CLASSIFY_HEAD_FORM", "0")), C.c_void_p(wsp + (-wsp) % 256), nbytes)
+
     def refresh_weights(self):
         """Re-pack every filter / bias from the live parameters into the plan's EXISTING device buffers (same shapes, same
         pointers: captured graphs stay valid).  Needed whenever weights or BatchNorm running statistics changed behind torch's
@@ -943,6 +981,10 @@ class Engine:
                 if swp is not None:
                     self.be.assign(swp, stem[0])
                     self.be.assign(sbp, stem[1])
+            for lin, wp, bp in self._linear_bufs:
+                w, b = self._linear_weights(lin)
+                self.be.assign(wp, w)
+                self.be.assign(bp, b)
             new_anchors = self._det.anchors.detach().float().cpu().clone() if self._det is not None else None
             if new_anchors is not None and self._anchor_ops and not torch.equal(new_anchors, self.anchors):
                 self.anchors = new_anchors

@@ -430,3 +430,69 @@ class ModelEMA:
             pr[3][key] = tab
         _lib.check(lib.y5_mt_lerp(C.c_void_p(tab[0].data_ptr()), len(todo), tab[1], float(d), stream), lib)
         _state.bump_weights_epoch()
+
+
+# ---- classification (utils/torch_utils.py:52-58, 73-93) -----------------------------------------------------------------------------------
+def classify_post(logits, labels=None, label_smoothing=0.0, want_probs=True):
+    """One launch of y5_classify_post (csrc/classify.h) on a batch of logits (B, nc) fp16 / fp32: (top5 (B, 5) int32 -- the first min(5, nc)
+    columns of argsort(1, descending=True), equal values by ascending index, unused columns -1; probs (B, nc) fp32 softmax or None; row_loss (B)
+    fp32 cross-entropy with label smoothing per row, or None without labels).  No host synchronisation."""
+    import ctypes as C
+
+    if not (torch.is_tensor(logits) and _libm.accepts(logits)):
+        raise RuntimeError("yolov5_amd: classify_post needs logits on the GPU (there is no CPU execution path)")
+    if logits.ndim != 2 or logits.dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"classify_post: expected (B, nc) fp16 / fp32 logits, got {logits.dtype} {tuple(logits.shape)}")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    B, nc = logits.shape
+    dev = logits.device
+    top5 = torch.empty((B, 5), dtype=torch.int32, device=dev)
+    probs = torch.empty((B, nc), dtype=torch.float32, device=dev) if want_probs else None
+    lab = loss = None
+    if labels is not None:
+        lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+        if lab.shape != (B,):
+            raise ValueError(f"classify_post: expected {B} labels, got {tuple(lab.shape)}")
+        loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    lib = _libm.lib()
+    rc = lib.y5_classify_post(p(logits), _libm.Y5_F16 if logits.dtype == torch.float16 else _libm.Y5_F32, B, nc, logits.stride(0), p(lab),
+                              float(label_smoothing), p(top5), p(probs), p(loss), _libm.stream(dev))
+    _libm.check(rc, lib)
+    return top5, probs, loss
+
+
+class _HipCrossEntropyLoss(nn.Module):
+    """nn.CrossEntropyLoss(label_smoothing=...) (reduction 'mean') on device logits: the per-row losses come from y5_classify_post, their mean is
+    one torch reduction on the device.  Forward only -- classification training is not built."""
+
+    def __init__(self, label_smoothing=0.0):
+        super().__init__()
+        self.label_smoothing = float(label_smoothing)
+
+    def forward(self, logits, labels):
+        return classify_post(logits, labels, self.label_smoothing, want_probs=False)[2].mean()
+
+
+def smartCrossEntropyLoss(label_smoothing=0.0):
+    """utils/torch_utils.py:52-58."""
+    return _HipCrossEntropyLoss(label_smoothing)
+
+
+def reshape_classifier_output(model, n=1000):
+    """utils/torch_utils.py:73-93, the Classify branch: give the head's Linear `n` outputs (a new, randomly initialised layer) unless it has them.
+    The torchvision branches (a bare nn.Linear / nn.Sequential last layer) are not built."""
+    from .common import Classify
+
+    name, m = list((model.model if hasattr(model, "model") else model).named_children())[-1]  # last module
+    if not isinstance(m, Classify):
+        raise NotImplementedError(f"reshape_classifier_output: only a Classify head is supported, the last module is {type(m).__name__}")
+    if m.linear.out_features != n:
+        old = m.linear
+        m.linear = nn.Linear(old.in_features, n).to(device=old.weight.device, dtype=old.weight.dtype)
+        for owner in (model, getattr(model, "model", None)):
+            if hasattr(owner, "invalidate_engine"):
+                owner.invalidate_engine()  # (the cached plans hold the old Linear's shape)
+        if hasattr(model, "nc"):
+            model.nc = n

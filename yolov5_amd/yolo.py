@@ -1,5 +1,5 @@
 """Model classes with the reference's names and API (models/yolo.py): Detect :71-128, Segment :131-150,
-BaseModel :153-212, DetectionModel :215-327, SegmentationModel :333, parse_model :375-458.
+BaseModel :153-212, DetectionModel :215-327, SegmentationModel :333, ClassificationModel :343-372, parse_model :375-458.
 
 Eval-mode `forward` is one call into the HIP execution plan (yolov5_amd.engine); what it returns matches the
 reference: `(z[bs, N, no], [raw_i[bs, na, ny, nx, no]])`, `(z,)` when `Detect.export` is set (AutoShape), and
@@ -19,7 +19,7 @@ from torch import nn
 
 from . import _lib, _state
 from .cfg import load_cfg
-from .common import C3, SPPF, Bottleneck, Concat, Conv, Proto
+from .common import C3, SPPF, Bottleneck, Classify, Concat, Conv, DetectMultiBackend, Proto
 from .general import LOGGER, make_divisible
 from .packing import fuse_conv_bn_weights
 
@@ -84,6 +84,15 @@ class BaseModel(nn.Module):
             return train_forward(self, x)  # list of raw (bs, na, ny, nx, no) maps, differentiable w.r.t. the parameters
         det = self.model[-1]
         want_raw = not getattr(det, "export", False)
+        out = self._plan_forward(x, want_raw)
+        z = out["z"]
+        raw = [out[f"raw{i}"] for i in range(det.nl)] if want_raw else None
+        if isinstance(det, Segment):
+            return (z, out["proto"]) if not want_raw else (z, out["proto"], raw)
+        return (z,) if not want_raw else (z, raw)
+
+    def _plan_forward(self, x, want_raw, split=True):
+        """The outputs of this model's cached plan for input `x` (built on first use, filters re-packed when the weights changed)."""
         key = (tuple(x.shape), next(self.parameters()).dtype, str(x.device), want_raw)
         cache = self._engines
         eng = cache.get(key)
@@ -92,7 +101,7 @@ class BaseModel(nn.Module):
             from .engine import Engine, SplitEngine
 
             parts = 2 if _lib.experimental("split2") else 1
-            if x.is_cuda and parts > 1 and x.shape[0] >= 16 * parts and x.shape[0] % parts == 0:
+            if split and x.is_cuda and parts > 1 and x.shape[0] >= 16 * parts and x.shape[0] % parts == 0:
                 # opt-in (Y5_EXPERIMENTAL=split2): sub-batch plans on separate streams fill each other's kernel tails (engine.SplitEngine;
                 # +3 % images/s on yolov5s bs=64, but per-kernel figures then describe overlapped launches)
                 eng = SplitEngine(self, tuple(x.shape), key[1], x.device, want_raw=want_raw, parts=parts)
@@ -109,12 +118,7 @@ class BaseModel(nn.Module):
             if eng._stamp != stamp:  # weights / BN statistics changed since the filters were packed: re-pack, keep plan + graphs
                 eng.refresh_weights()
                 eng._stamp = stamp
-        out = eng(x)
-        z = out["z"]
-        raw = [out[f"raw{i}"] for i in range(det.nl)] if want_raw else None
-        if isinstance(det, Segment):
-            return (z, out["proto"]) if not want_raw else (z, out["proto"], raw)
-        return (z,) if not want_raw else (z, raw)
+        return eng(x)
 
     @property
     def _engines(self):
@@ -297,6 +301,43 @@ class SegmentationModel(DetectionModel):
 
     def __init__(self, cfg="yolov5s-seg.yaml", ch=3, nc=None, anchors=None):
         super().__init__(cfg, ch, nc, anchors)
+
+
+class ClassificationModel(BaseModel):
+    """models/yolo.py:343-372: a detection backbone cut at `cutoff` with a Classify head in place of its last layer.  Inference only:
+    eval-mode forward returns the (B, nc) logits of the HIP plan, a fresh tensor per call."""
+
+    def __init__(self, cfg=None, model=None, nc=1000, cutoff=10):
+        super().__init__()
+        self._from_detection_model(model, nc, cutoff) if model is not None else self._from_yaml(cfg)
+
+    def _from_detection_model(self, model, nc=1000, cutoff=10):
+        """models/yolo.py:353-368."""
+        if isinstance(model, DetectMultiBackend):
+            model = model.model  # unwrap DetectMultiBackend
+        model.model = model.model[:cutoff]  # backbone
+        m = model.model[-1]  # last layer
+        ch = m.conv.in_channels if hasattr(m, "conv") else m.cv1.conv.in_channels  # ch into module
+        c = Classify(ch, nc)
+        c.i, c.f, c.type = m.i, m.f, "models.common.Classify"  # index, from, type
+        model.model[-1] = c  # replace
+        self.model = model.model
+        self.stride = model.stride
+        self.save = []
+        self.nc = nc
+        if hasattr(model, "invalidate_engine"):
+            model.invalidate_engine()  # (the donor's cached plans describe a module tree that no longer exists)
+
+    def _from_yaml(self, cfg):
+        """models/yolo.py:370-372: a placeholder in the reference too."""
+        raise NotImplementedError("ClassificationModel from a *.yaml config is not built (a placeholder in the reference as well); pass model=")
+
+    def forward(self, x, augment=False, profile=False):
+        if augment:
+            raise NotImplementedError("ClassificationModel: augmented inference does not apply to classification")
+        if self.training:
+            raise NotImplementedError("ClassificationModel: classification training (Classify backward, classify/train.py) is not built; call .eval()")
+        return self._plan_forward(x, False, split=False)["logits"]
 
 
 def initialize_weights(model):
