@@ -451,7 +451,7 @@ int y5_letterbox_batch(const y5_letterbox_job* jobs_dev, int B, int H, int W, in
 
 /* ---------------------------------------------------------------------------------------------------------
  * Classification (models/common.py:1120-1140 Classify, utils/augmentations.py:297-341 classify_transforms,
- * classify/predict.py:120-153, classify/val.py:104-147).  Inference only.
+ * classify/predict.py:120-153, classify/val.py:104-147; training: classify/train.py:200-252).
  *
  * y5_classify_transform_batch -- classify_transforms(S) for a ragged batch of u8 HWC BGR frames in one launch: centre crop of
  *   m = min(h0, w0) pixels at top = (h0 - m) / 2, left = (w0 - m) / 2, cv2.resize(crop, (S, S), INTER_LINEAR) (the restated 8-bit
@@ -485,6 +485,35 @@ int y5_classify_head(const void* x, int dtype, int B, int HW, int C, int ld, con
                      int form, void* workspace, size_t workspace_bytes, void* stream);
 int y5_classify_post(const void* logits, int dtype, int B, int nc, int ld, const int* labels, float label_smoothing, int* top5, float* probs,
                      float* row_loss, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Classification training (csrc/classify_train.h has the launch structure and the Dropout stream's exact layout).
+ *
+ * y5_classify_head_train -- models/common.py:1137-1140 in train mode, `linear(drop(pool(x).flatten(1)))`: form 2 of y5_classify_head
+ *   with the pooled rows (B, C) fp32 left in the caller's `pooled` buffer (>= y5_classify_head_workspace_bytes(B, C) bytes, 16-byte
+ *   aligned, else Y5_ERR_WORKSPACE) and nn.Dropout(p_drop) applied to them in place before the Linear: element i = b * C + c is kept
+ *   iff (philox4x32_10(key = seed, counter = i)[0] >> 8) * 2^-24 >= p_drop, kept values are divided by (1 - p_drop), p_drop == 1 gives
+ *   zeros.  p_drop == 0 launches no Dropout kernel: the logits equal y5_classify_head(form = 2) bit for bit.  Not torch's stream.
+ *
+ * y5_classify_head_bwd -- the backward of that op (what autograd derives from models/common.py:1140).  dlogits: (B, nc) in `dtype`,
+ *   `ldd` elements per row; pooled_d: the post-Dropout rows the forward left; w: (nc, C) in `dtype`; (p_drop, seed): the forward's.
+ *     dbias[j] = sum_b dlogits[b, j]                      (nc) fp32, written
+ *     dw[j, c] = sum_b dlogits[b, j] * pooled_d[b, c]     (nc, C) fp32, written
+ *     dx[b, pixel, c] = (sum_j dlogits[b, j] * w[j, c]) * keep(b, c) / (1 - p_drop) / HW     (B, HW, C) in `dtype`, `ld` per pixel
+ *   fp32 accumulation (Y5_F16: v_mfma_f32_32x32x16_f16, pooled_d as hi + lo fp16 halves), no atomics, every sum in an order fixed by
+ *   (B, nc, C, HW); dx of image b equals the single-row call bit for bit.  workspace: y5_classify_head_workspace_bytes(B, C) bytes.
+ *   Argument rules of y5_classify_head.
+ *
+ * y5_classify_ce_bwd -- gradient of nn.CrossEntropyLoss(label_smoothing, reduction='none') rows (classify/train.py:214-219,
+ *   utils/torch_utils.py:52-58): dlogits[b, j] = grad_rows[b] * (softmax(z_b)_j - (1 - eps) [j == y_b] - eps / nc) in the logits' dtype,
+ *   `ldd` elements per row; grad_rows: (B) fp32 on the device; a label outside [0, nc) gives a NaN row.  nc <= 36864.
+ * ------------------------------------------------------------------------------------------------------- */
+int y5_classify_head_train(const void* x, int dtype, int B, int HW, int C, int ld, const void* w, const float* bias, int nc, void* logits, int ldo,
+                           float* pooled, size_t pooled_bytes, float p_drop, unsigned long long seed, void* stream);
+int y5_classify_head_bwd(const void* dlogits, int dtype, int B, int nc, int ldd, const float* pooled_d, const void* w, int HW, int C, float p_drop,
+                         unsigned long long seed, float* dbias, float* dw, void* dx, int ld, void* workspace, size_t workspace_bytes, void* stream);
+int y5_classify_ce_bwd(const void* logits, int dtype, int B, int nc, int ld, const int* labels, float label_smoothing, const float* grad_rows,
+                       void* dlogits, int ldd, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * y5_val_match -- val.py:296-307 for every image of a batch in one launch: de-letterbox the predictions and the labels

@@ -11,6 +11,7 @@
 #include "conv_cfgs.h"
 #include "y5_host.h"
 #include "classify.h"   // y5_classify_head, y5_classify_post: the classification head and its post-processing
+#include "classify_train.h"   // y5_classify_head_train, y5_classify_head_bwd, y5_classify_ce_bwd: its training side
 
 extern "C" int y5_detect_head_fwd_hint(const y5_conv_desc* d, const void* x, const void* w_packed, const float* bias, int ny, int nx, float stride,
                                        const float* anchors_px, void* z, long long nrows_total, long long row_off, void* obj_hint, void* stream_) {

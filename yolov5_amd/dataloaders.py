@@ -650,9 +650,11 @@ class ClassificationLoader:
     """`ClassificationDataset.__getitem__`'s torch_transforms branch plus the default collate, on frames already in memory: yields
     (images (b, 3, imgsz, imgsz) fp32 | fp16, labels (b) int64) on the device, ONE transform launch per batch (augmentations.classify_transform_batch).
     frames: uint8 HWC BGR images of any sizes (device tensors, or host arrays uploaded per batch); the last batch may be short.  Reading image folders,
-    the RAM / disk caches and the train-time albumentations branch are not built."""
+    the RAM / disk caches and the train-time albumentations branch are not built.  shuffle=True: a fresh torch.randperm per epoch (per __iter__)
+    from the loader's own generator seeded with `seed` -- repeatable, but NOT the order of the reference's DataLoader (whose sampler draws from
+    torch's global generator through its own base seed)."""
 
-    def __init__(self, frames, labels, imgsz=224, batch_size=64, half=False, device=None):
+    def __init__(self, frames, labels, imgsz=224, batch_size=64, half=False, device=None, shuffle=False, seed=0):
         if len(frames) != len(labels):
             raise ValueError(f"ClassificationLoader: {len(frames)} frames, {len(labels)} labels")
         self.frames, self.imgsz, self.batch_size, self.half = list(frames), int(imgsz), int(batch_size), half
@@ -662,6 +664,8 @@ class ClassificationLoader:
             raise ValueError("ClassificationLoader: host frames need a device=")
         self.device = torch.device(device)
         self.labels = torch.as_tensor(np.asarray(labels), dtype=torch.int64).to(self.device)
+        self.shuffle = bool(shuffle)
+        self._gen = torch.Generator().manual_seed(int(seed)) if self.shuffle else None
 
     def __len__(self):
         return (len(self.frames) + self.batch_size - 1) // self.batch_size
@@ -669,6 +673,13 @@ class ClassificationLoader:
     def __iter__(self):
         from .augmentations import classify_transform_batch
 
+        if self.shuffle:
+            order = torch.randperm(len(self.frames), generator=self._gen)
+            for b0 in range(0, len(self.frames), self.batch_size):
+                ids = order[b0:b0 + self.batch_size]
+                ims = [self.frames[i] for i in ids.tolist()]
+                yield classify_transform_batch(ims, self.imgsz, half=self.half, device=self.device), self.labels[ids.to(self.device)]
+            return
         for b0 in range(0, len(self.frames), self.batch_size):
             ims = self.frames[b0:b0 + self.batch_size]
             yield classify_transform_batch(ims, self.imgsz, half=self.half, device=self.device), self.labels[b0:b0 + len(ims)]

@@ -463,15 +463,56 @@ def classify_post(logits, labels=None, label_smoothing=0.0, want_probs=True):
     return top5, probs, loss
 
 
+def classify_ce_bwd(logits, labels, label_smoothing, grad_rows):
+    """One launch of y5_classify_ce_bwd (csrc/classify_train.h): dlogits (B, nc) in the logits' dtype for the per-row cross-entropy losses of
+    classify_post, `grad_rows` (B) being the gradient that reaches those rows.  No host synchronisation."""
+    import ctypes as C
+
+    if not (torch.is_tensor(logits) and _libm.accepts(logits)):
+        raise RuntimeError("yolov5_amd: classify_ce_bwd needs logits on the GPU (there is no CPU execution path)")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    B, nc = logits.shape
+    dev = logits.device
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    g = grad_rows.to(device=dev, dtype=torch.float32).contiguous()
+    if lab.shape != (B,) or g.shape != (B,):
+        raise ValueError(f"classify_ce_bwd: expected {B} labels and row gradients, got {tuple(lab.shape)}, {tuple(g.shape)}")
+    out = torch.empty((B, nc), dtype=logits.dtype, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    lib = _libm.lib()
+    rc = lib.y5_classify_ce_bwd(p(logits), _libm.Y5_F16 if logits.dtype == torch.float16 else _libm.Y5_F32, B, nc, logits.stride(0), p(lab),
+                                float(label_smoothing), p(g), p(out), nc, _libm.stream(dev))
+    _libm.check(rc, lib)
+    return out
+
+
+class _CrossEntropyRowsFn(torch.autograd.Function):
+    """logits -> per-row cross-entropy losses: forward is the classify_post launch, backward the y5_classify_ce_bwd launch."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, eps):
+        ctx.save_for_backward(logits, labels)
+        ctx.eps = eps
+        return classify_post(logits, labels, eps, want_probs=False)[2]
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        logits, labels = ctx.saved_tensors
+        return classify_ce_bwd(logits, labels, ctx.eps, grad_rows), None, None
+
+
 class _HipCrossEntropyLoss(nn.Module):
     """nn.CrossEntropyLoss(label_smoothing=...) (reduction 'mean') on device logits: the per-row losses come from y5_classify_post, their mean is
-    one torch reduction on the device.  Forward only -- classification training is not built."""
+    one torch reduction on the device; the gradient of logits that require one is one y5_classify_ce_bwd launch."""
 
     def __init__(self, label_smoothing=0.0):
         super().__init__()
         self.label_smoothing = float(label_smoothing)
 
     def forward(self, logits, labels):
+        if torch.is_tensor(logits) and logits.requires_grad and torch.is_grad_enabled():
+            return _CrossEntropyRowsFn.apply(logits, labels, self.label_smoothing).mean()
         return classify_post(logits, labels, self.label_smoothing, want_probs=False)[2].mean()
 
 

@@ -90,6 +90,7 @@ class TrainEngine:
         self.raw = {}
         self.seg = False
         self.proto = None
+        self.cls = None   # classification plan: state of the pool + Dropout + Linear op behind the head's Conv (csrc/classify_train.h)
         self.convs = []
         self._dw_total = 0
         self._keep = []
@@ -123,6 +124,19 @@ class TrainEngine:
                 self.raw[op["level"]] = None  # allocated per forward: the caller owns the returned maps (models/yolo.py:98)
             elif op["op"] == "to_nchw":
                 self.seg = True  # Segment head: the forward also returns proto (models/yolo.py:150)
+            elif op["op"] == "classify_head":
+                lin, xh = op["mod"], op["x"]
+                if lin.in_features != xh.C:
+                    raise ValueError(f"classify head: Linear expects {lin.in_features} channels, the convolution delivers {xh.C}")
+                if lin.bias is None:
+                    raise NotImplementedError("classification training expects the head's Linear to have a bias (models/common.py:1135)")
+                head = next(m for m in model.modules() if getattr(m, "linear", None) is lin)
+                # pooled: the post-Dropout rows (B, C) fp32, the op's saved activation; ws: the backward's per-image gradient rows; w16: fp16 plans
+                # read an fp16 copy of the Linear weight, refreshed from the fp32 master at every forward
+                self.cls = dict(op=op, lin=lin, head=head, nbytes=int(self.lib.y5_classify_head_workspace_bytes(B, xh.C)),
+                                pooled=self.be.empty((B, xh.C), torch.float32), ws=self.be.empty((B, xh.C), torch.float32),
+                                w16=self.be.empty((op["nc"], xh.C), torch.float16) if dtype == torch.float16 else None, p=0.0, seed=0, wptr=0)
+                self.logits = None
         self.dz = self.be.empty((max(max_z, 8),), f16)
         self.dwflat = self.be.empty((max(self._dw_total, 64),), torch.float32)  # packed fp32 dW accumulators of all convs
         self.ws = self.be.empty((max(max_ws, 256),), torch.uint8)
@@ -331,11 +345,34 @@ class TrainEngine:
                 s = op["src"]
                 self.proto = be.empty((B, s.C, s.H, s.W), self.dtype)
                 _lib.check(lib.y5_nhwc_to_nchw(_vp(self._ptr(s)), self.dt, _vp(be.ptr(self.proto)), B, s.C, s.H, s.W, self._ld(s), stm), lib)
+            elif kind == "classify_head":
+                self._fwd_classify(op, stm)
             else:
                 raise NotImplementedError(kind)
         if self._nbt:
             torch._foreach_add_(self._nbt, 1)  # BatchNorm2d.num_batches_tracked of every layer: one launch instead of 57
+        if self.cls is not None:
+            return [self.logits]
         return [self.raw[i] for i in sorted(self.raw)] + ([self.proto] if self.seg else [])
+
+    def _fwd_classify(self, op, stm):
+        """Train-mode `linear(drop(pool(x).flatten(1)))` (models/common.py:1137-1140): y5_classify_head_train.  The Dropout probability is read
+        from the module at every forward (classify/train.py:157-158 sets it after construction); with p > 0 ONE seed per forward comes from
+        torch's default CPU generator (torch.manual_seed makes a run repeatable), the backward regenerates the mask from it."""
+        lib, be, B = self.lib, self.be, self.spec.B
+        cl, xh, nc = self.cls, op["x"], op["nc"]
+        lin = cl["lin"]
+        p = float(cl["head"].drop.p)
+        cl["p"], cl["seed"] = p, (int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if p > 0 else 0)
+        if cl["w16"] is not None:
+            with torch.no_grad():
+                be.assign(cl["w16"], lin.weight.detach())
+            cl["wptr"] = be.ptr(cl["w16"])
+        else:
+            cl["wptr"] = self._f32(lin.weight)
+        self.logits = be.empty((B, nc), self.dtype)   # fresh per call: the caller owns it (fp16 on the fp16 plan, like the reference under autocast)
+        _lib.check(lib.y5_classify_head_train(_vp(self._ptr(xh)), self.dt, B, xh.H * xh.W, xh.C, self._ld(xh), _vp(cl["wptr"]), _vp(self._f32(lin.bias)), nc,
+                                              _vp(be.ptr(self.logits)), nc, _vp(be.ptr(cl["pooled"])), cl["nbytes"], p, cl["seed"], stm), lib)
 
     def _fwd_conv(self, st, stm):
         lib, be, B = self.lib, self.be, self.spec.B
@@ -406,14 +443,27 @@ class TrainEngine:
                                                         _vp(self._ptr(res)) if res is not None else None, self._ld(res) if res is not None else 0,
                                                         _vp(self._ptr(y)), self._ld(y), stm), lib)
             else:
-                _lib.check(lib.y5_bn_silu_fwd(_vp(be.ptr(st["z"])), self.dt, npix, c2, c2, _vp(st["gamma"]), _vp(st["beta"]), float(bn.eps),
-                                              float(bn.momentum if bn.momentum is not None else 0.1), rm, rv, _vp(be.ptr(st["mean"])),
-                                              _vp(be.ptr(st["invstd"])), _vp(self._ptr(res)) if res is not None else None,
-                                              self._ld(res) if res is not None else 0, _vp(self._ptr(y)), self._ld(y), _vp(be.ptr(self.ws)),
-                                              self.ws_bytes, stm), lib)
+                for o, n in self._bn_chunks(c2):   # (one launch; two for the fp32 plan's 1280-channel Classify convolution)
+                    _lib.check(lib.y5_bn_silu_fwd(_vp(be.ptr(st["z"]) + o * self.es), self.dt, npix, n, c2, _vp(st["gamma"] + 4 * o), _vp(st["beta"] + 4 * o),
+                                                  float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.1),
+                                                  _vp(rm.value + 4 * o) if rm is not None else None, _vp(rv.value + 4 * o) if rv is not None else None,
+                                                  _vp(be.ptr(st["mean"]) + 4 * o), _vp(be.ptr(st["invstd"]) + 4 * o),
+                                                  _vp(self._ptr(res) + o * self.es) if res is not None else None, self._ld(res) if res is not None else 0,
+                                                  _vp(self._ptr(y) + o * self.es), self._ld(y), _vp(be.ptr(self.ws)), self.ws_bytes, stm), lib)
             self._running_done(bn)
         if y2 is not None:
             _lib.check(lib.y5_upsample2x(_vp(self._ptr(y)), self.dt, _vp(self._ptr(y2)), B, y.H, y.W, y.C, self._ld(y), self._ld(y2), stm), lib)
+
+    def _bn_chunks(self, c2):
+        """(channel offset, channels) of the BatchNorm launches of a c2-channel layer: the kernels of csrc/bn.hip take at most 256 16-byte vectors
+        of channels (2048 fp16 / 1024 fp32) -- every layer of the detection and segmentation models in one launch; the 1280-channel convolution
+        of the Classify head on the fp32 plan is the one layer that takes two (BatchNorm is per channel: the slices are independent)."""
+        limit = 256 * (16 // self.es)
+        if c2 <= limit:
+            return [(0, c2)]
+        n = -(-c2 // limit)
+        step = round_up(-(-c2 // n), 16)
+        return [(o, min(step, c2 - o)) for o in range(0, c2, step)]
 
     @staticmethod
     def _sync_world(bn):
@@ -527,6 +577,20 @@ class TrainEngine:
                     _lib.check(lib.y5_train_glue_f32(4, _vp(self._ptr(b)), _vp(self._ptr(b, True)), B, b.H, b.W, op["C"], self._ld(b), self._ld(b), op["k"], stm), lib)
             elif kind == "conv":
                 self._bwd_conv(op["_st"], stm, is_written, mark, grads, hold)
+            elif kind == "classify_head":
+                cl, xh = self.cls, op["x"]
+                lin = cl["lin"]
+                dph, dpp, ddt = be.input(dps[0])
+                if ddt != self.dt or tuple(dph.shape) != (B, op["nc"]):
+                    raise TypeError(f"classify head backward: expected a ({B}, {op['nc']}) {self.dtype} gradient of the logits")
+                hold.append(dph)
+                # dbias / dW go straight into the Linear's slots of the gradient arena, dx into the gradient buffer of the head convolution's output
+                _lib.check(lib.y5_classify_head_bwd(_vp(dpp), self.dt, B, op["nc"], op["nc"], _vp(be.ptr(cl["pooled"])), _vp(cl["wptr"]), xh.H * xh.W, xh.C,
+                                                    cl["p"], cl["seed"], _vp(self._gptr(lin.bias)), _vp(self._gptr(lin.weight)), _vp(self._ptr(xh, True)),
+                                                    self._ld(xh), _vp(be.ptr(cl["ws"])), cl["nbytes"], stm), lib)
+                mark(xh)
+                grads[self._pidx[id(lin.weight)]] = True
+                grads[self._pidx[id(lin.bias)]] = True
             elif kind == "to_nhwc":
                 pass
             elif kind == "to_nchw":  # dproto (NCHW) -> NHWC gradient of proto.cv3's output; Proto's input (the P3 feature) then fans in with Detect level 0
@@ -643,10 +707,12 @@ class TrainEngine:
                                                         _vp(st["beta"]), _vp(be.ptr(st["mean"])), _vp(be.ptr(st["invstd"])), _vp(be.ptr(gs)),
                                                         _vp(be.ptr(gs) + 4 * c2), y.H * y.W * self._sync_images(m.bn, world), _vp(be.ptr(self.dz)), c2, stm), lib)
             else:
-                _lib.check(lib.y5_bn_silu_bwd(_vp(self._ptr(y, True)), self._ld(y), _vp(be.ptr(st["z"])), c2, self.dt, npix, c2,
-                                              _vp(st["gamma"]), _vp(st["beta"]), _vp(be.ptr(st["mean"])), _vp(be.ptr(st["invstd"])),
-                                              _vp(be.ptr(self.dz)), c2, _vp(self._gptr(m.bn.weight)), _vp(self._gptr(m.bn.bias)),
-                                              _vp(be.ptr(self.ws)), self.ws_bytes, stm), lib)
+                for o, n in self._bn_chunks(c2):
+                    _lib.check(lib.y5_bn_silu_bwd(_vp(self._ptr(y, True) + o * self.es), self._ld(y), _vp(be.ptr(st["z"]) + o * self.es), c2, self.dt, npix, n,
+                                                  _vp(st["gamma"] + 4 * o), _vp(st["beta"] + 4 * o), _vp(be.ptr(st["mean"]) + 4 * o),
+                                                  _vp(be.ptr(st["invstd"]) + 4 * o), _vp(be.ptr(self.dz) + o * self.es), c2,
+                                                  _vp(self._gptr(m.bn.weight) + 4 * o), _vp(self._gptr(m.bn.bias) + 4 * o),
+                                                  _vp(be.ptr(self.ws)), self.ws_bytes, stm), lib)
             dz_ptr, ld_dz = be.ptr(self.dz), c2
             grads[self._pidx[id(m.bn.weight)]] = True
             grads[self._pidx[id(m.bn.bias)]] = True
@@ -758,7 +824,7 @@ class _TrainFn(torch.autograd.Function):
 
 def train_forward(model, x):
     """Train-mode `BaseModel._forward_once` (models/yolo.py:160-170): list of (bs, na, ny, nx, no) tensors; for a Segment head
-    (p, proto) with proto (bs, nm, mh, mw) (models/yolo.py:150)."""
+    (p, proto) with proto (bs, nm, mh, mw) (models/yolo.py:150); for a Classify head the (bs, nc) logits tensor."""
     # fp32 images -> the fp32 plan (reference-precision mode: train.py without AMP); fp16 / uint8 images -> the fp16 (AMP) plan
     dtype = torch.float32 if x.dtype == torch.float32 else torch.float16
     key = (tuple(x.shape), str(x.device), dtype)
@@ -770,4 +836,6 @@ def train_forward(model, x):
         cache[key] = eng
     eng.grad_sink = model.__dict__.get("_ddp_sink")
     outs = list(_TrainFn.apply(eng, x, *eng.params))
+    if eng.cls is not None:
+        return outs[0]  # ClassificationModel: the (bs, nc) logits (models/common.py:1140)
     return (outs[:-1], outs[-1]) if eng.seg else outs  # Segment: (p, proto) (models/yolo.py:150)

@@ -304,8 +304,8 @@ class SegmentationModel(DetectionModel):
 
 
 class ClassificationModel(BaseModel):
-    """models/yolo.py:343-372: a detection backbone cut at `cutoff` with a Classify head in place of its last layer.  Inference only:
-    eval-mode forward returns the (B, nc) logits of the HIP plan, a fresh tensor per call."""
+    """models/yolo.py:343-372: a detection backbone cut at `cutoff` with a Classify head in place of its last layer.  The eval-mode
+    forward returns the (B, nc) logits of the HIP plan, the train-mode forward those of the training plan (train_engine.py); a fresh tensor per call."""
 
     def __init__(self, cfg=None, model=None, nc=1000, cutoff=10):
         super().__init__()
@@ -336,7 +336,11 @@ class ClassificationModel(BaseModel):
         if augment:
             raise NotImplementedError("ClassificationModel: augmented inference does not apply to classification")
         if self.training:
-            raise NotImplementedError("ClassificationModel: classification training (Classify backward, classify/train.py) is not built; call .eval()")
+            if not _lib.accepts(x):
+                raise NotImplementedError("ClassificationModel: classification training has no CPU execution path; move the model and the images to the GPU")
+            from .train_engine import train_forward
+
+            return train_forward(self, x)  # (B, nc) logits, differentiable w.r.t. the parameters (classify/train.py:213)
         return self._plan_forward(x, False, split=False)["logits"]
 
 
