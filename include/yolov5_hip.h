@@ -450,6 +450,36 @@ int y5_letterbox_batch(const y5_letterbox_job* jobs_dev, int B, int H, int W, in
                        int dst_chw, int div255, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * y5_letterbox_area_batch -- the validation image path of a detection dataset for a ragged batch in one launch:
+ *   utils/dataloaders.py:784-788 `load_image` (cv2.resize with INTER_AREA when the image shrinks and augment is off, INTER_LINEAR
+ *   when it grows), :715-716 `letterbox(auto=False, scaleup=False)` -- pure padding with `pad_value` for the shapes a loader makes --,
+ *   :763 HWC -> CHW and BGR -> RGB; dst (B, 3, H, W) Y5_U8, Y5_F16 or Y5_F32 with the `/ 255` expressions of y5_letterbox_batch.
+ * jobs_dev: DEVICE array of B jobs; the first eight fields are y5_letterbox_job's.  mode selects the path:
+ *   Y5_AREA_COPY (nh == h0 && nw == w0), Y5_AREA_LINEAR (nh > h0 || nw > w0: the 8-bit INTER_LINEAR of y5_letterbox_batch, unchanged),
+ *   Y5_AREA_2X2 (both scales exactly 2: (a + b + c + d + 2) >> 2), Y5_AREA_INT (both scales integer, block iy x ix: integer sum s,
+ *   sat_u8(rint((float)s * (1.0f / (ix * iy)))) with the product in fp32), Y5_AREA_TAB (OpenCV's general INTER_AREA).
+ * tabs_dev: `tab_words` int32 words on the device, the tap tables of the Y5_AREA_TAB jobs.  Words xtab + 3 d .. + 2 (d < nw) and
+ *   ytab + 3 d .. + 2 (d < nh) hold {first source index, tap count n, word offset of n fp32 weights} of output index d; the taps of one
+ *   index are consecutive source indices.  The host builds them in double (computeResizeAreaTab): scale = (double)ssize / dsize,
+ *   f1 = d * scale, f2 = f1 + scale, cell = min(scale, ssize - f1), s1 = ceil(f1), s2 = min(floor(f2), ssize - 1), s1 = min(s1, s2);
+ *   tap (s1 - 1, (s1 - f1) / cell) if s1 - f1 > 1e-3; taps (s, 1 / cell) for s in [s1, s2); tap (s2, min(min(f2 - s2, 1), cell) / cell) if
+ *   f2 - s2 > 1e-3; weights rounded to fp32.  One output value: per source row of the y entry, in order, row = 0.f, row += (float)S * alpha
+ *   over the x taps in order; acc = beta * row for the first row, acc += beta * row after it; sat_u8(rint(acc)); every product and sum
+ *   rounded on its own.  An entry that points outside its image or the table is not followed (the pixel is written as pad_value).
+ * Restates OpenCV's published algorithm (modules/imgproc/src/resize.cpp); cv2 is absent here, so parity with the real library is
+ * unpinned by necessity, like INTER_LINEAR.  Every output value is an independent sum in a fixed order: bitwise repeatable.
+ * ------------------------------------------------------------------------------------------------------- */
+enum { Y5_AREA_COPY = 0, Y5_AREA_LINEAR = 1, Y5_AREA_2X2 = 2, Y5_AREA_INT = 3, Y5_AREA_TAB = 4 };
+typedef struct y5_area_job {
+  const void* src;
+  int h0, w0, stride;
+  int nw, nh, top, left;
+  int mode, ix, iy, xtab, ytab, reserved;
+} y5_area_job;
+int y5_letterbox_area_batch(const y5_area_job* jobs_dev, const int* tabs_dev, long long tab_words, int B, int H, int W, int pad_value,
+                            void* dst, int dst_dtype, int div255, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Classification (models/common.py:1120-1140 Classify, utils/augmentations.py:297-341 classify_transforms,
  * classify/predict.py:120-153, classify/val.py:104-147; training: classify/train.py:200-252).
  *
@@ -534,6 +564,24 @@ int y5_classify_ce_bwd(const void* logits, int dtype, int B, int nc, int ld, con
 int y5_val_match(const float* det, int ld_det, int max_det, const int* det_count, int bs, const float* labels, int ld_lab,
                  int nlabels, int img_col, int cls_col, int box_col, int xywh, const float* scale, const float* iouv, int niou,
                  unsigned char* correct, float* predn, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * y5_val_confusion -- utils/metrics.py:129-183 `ConfusionMatrix.process_batch` for every image of a batch in one launch, as val.py:289-309
+ * calls it per image; counts are added to `matrix` with integer atomics (their order cannot change the sums); no host synchronisation.
+ * det / det_count / max_det / bs, labels / ld_lab / nlabels / img_col / cls_col / box_col / xywh, scale: exactly as y5_val_match -- the
+ *            same device code de-letterboxes both sides and computes box_iou in fp32, so the IoUs are the bits process_batch sees.
+ *            det may be NULL with max_det == 0 (`detections=None`: every label is a background false negative).
+ * conf, iou_thres: detections with conf > `conf` take part; pairs with iou > `iou_thres` are candidates (both strict, classes ignored).
+ * Matching (:160-167) is two-stage: each detection keeps its highest-IoU label, then each label keeps the highest-IoU detection among
+ *            those that chose it.  Equal IoUs (argsort order in the reference, implementation-defined): the lower index wins.
+ * matrix:    (nc + 1, nc + 1) int32, row-major, ACCUMULATED into.  A matched label adds 1 at [det class, gt class]; an unmatched label
+ *            at [nc, gt class]; a detection above `conf` that ends without a label adds 1 at [det class, nc], but only in an image with
+ *            at least one match (the `if n:` of :180).  An image without labels adds nothing.  Classes are truncated to int; a class
+ *            outside [0, nc) is not counted.
+ * ------------------------------------------------------------------------------------------------------- */
+int y5_val_confusion(const float* det, int ld_det, int max_det, const int* det_count, int bs, const float* labels, int ld_lab,
+                     int nlabels, int img_col, int cls_col, int box_col, int xywh, const float* scale, float conf, float iou_thres,
+                     int nc, int* matrix, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * y5_val_match_masks -- the mask branch of process_batch (utils/metrics.py:239-249, masks=True; mask_iou of ultralytics.utils.metrics,

@@ -30,6 +30,7 @@ LIB_PATH = os.environ.get("Y5_LIB_PATH") or os.path.join(_HERE, "libyolov5_hip.s
 Y5_F16, Y5_F32, Y5_U8, Y5_I32 = 0, 1, 2, 3
 Y5_OK, Y5_ERR_BAD_ARG, Y5_ERR_UNSUPPORTED, Y5_ERR_RUNTIME, Y5_ERR_WORKSPACE = 0, -1, -2, -3, -4   # y5_status (include/yolov5_hip.h)
 NMS_MULTI_LABEL, NMS_AGNOSTIC = 1, 2
+AREA_COPY, AREA_LINEAR, AREA_2X2, AREA_INT, AREA_TAB = 0, 1, 2, 3, 4   # y5_area_job.mode
 
 
 class MaskImg(C.Structure):
@@ -80,6 +81,12 @@ class FilterJob(C.Structure):
 class LetterboxJob(C.Structure):
     """include/yolov5_hip.h: y5_letterbox_job (one image of a y5_letterbox_batch launch)."""
     _fields_ = [("src", C.c_void_p)] + [(n, C.c_int) for n in ("h0", "w0", "stride", "nw", "nh", "top", "left")]
+
+
+class AreaJob(C.Structure):
+    """include/yolov5_hip.h: y5_area_job (one image of a y5_letterbox_area_batch launch)."""
+    _fields_ = [("src", C.c_void_p)] + [(n, C.c_int) for n in ("h0", "w0", "stride", "nw", "nh", "top", "left", "mode", "ix", "iy", "xtab", "ytab",
+                                                                "reserved")]
 
 
 class ClassifyJob(C.Structure):
@@ -210,6 +217,8 @@ EXPORTS = {
     "y5_polygon_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_letterbox_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "y5_letterbox_area_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p]),
     "y5_classify_transform_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "y5_classify_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "y5_classify_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -224,6 +233,8 @@ EXPORTS = {
                                             C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "y5_val_match": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y5_val_confusion": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "y5_val_match_masks_ws_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "y5_val_match_masks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,

@@ -20,6 +20,7 @@
 #include "y5_host.h"
 #include "resize_u8.h"
 #include "classify_data.h"   // y5_classify_transform_batch: the classification transform (CenterCrop + ToTensor + Normalize)
+#include "val_data.h"        // y5_letterbox_area_batch: load_image (INTER_AREA / INTER_LINEAR) + pad of a detection validation batch
 
 namespace {
 constexpr int PX = 8;  // output pixels per lane

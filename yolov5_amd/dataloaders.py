@@ -12,11 +12,15 @@ Segmentation datasets (utils/segment/dataloaders.py:130-301 `LoadImagesAndLabels
 second half of this file -- `draw_sample_seg`, `seg_mosaic_batch`, `SegMosaicLoader`, `seg_letterbox_batch`, `SegValLoader`.  The image half
 is the SAME `y5_mosaic_batch` launch; the polygons go through the reference's own float64 expressions on the host and ONE `y5_polygon_masks`
 call (csrc/seg_data.h) rasterises, shrinks, orders and flips the masks of the batch.
-Not covered: rect batches / augment = False of detection datasets (the validation loader: augmentations.letterbox_batch), copy_paste,
+Detection validation (`LoadImagesAndLabels(augment=False, rect=..., pad=...)`, :589-612 rect ordering and batch shapes, :710-736 the letterbox
+branch, :784-788 `load_image` with INTER_AREA for a down-scale, + `collate_fn`): the third part of this file -- `area_jobs`,
+`letterbox_area_batch` (ONE `y5_letterbox_area_batch` launch per batch, csrc/val_data.h) and `ValLoader`.
+Not covered: reading images and label files from disk and the caches, image_weights, rect batches for TRAINING, collate_fn4, copy_paste,
 albumentations, perspective != 0."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import random
 
@@ -575,12 +579,13 @@ class SegMosaicLoader(MosaicLoader):
         self.epoch += 1
 
 
-def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, normalize=False, overlap=True, mask_ratio=1):
+def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, normalize=False, overlap=True, mask_ratio=1, area=False):
     """The augment = False, rect = False branch of the segmentation `__getitem__` (utils/segment/dataloaders.py:144-199) + collate_fn for the
     images `ids`: load_image, letterbox(auto=False, scaleup=False), labels and polygons to pixels with the float pad; the polygons are NOT
     resampled (own lengths); no warp, no HSV, no flips.  The image half is a `y5_mosaic_batch` launch with one-tile jobs on an s x s canvas and
-    the identity map.  load_image's INTER_AREA for a down-scale without augmentation (dataloaders.py:784) is not restated: an image larger
-    than s is shrunk with INTER_LINEAR, as in the training branch.
+    the identity map.  area=False (default, what tests/golden/seg_data_val.npz pins): an image larger than s is shrunk with INTER_LINEAR, as in
+    the training branch; area=True: the image half is ONE `y5_letterbox_area_batch` launch instead, which shrinks with load_image's INTER_AREA
+    (dataloaders.py:787) -- the same bits for every image that is copied or enlarged.
     Returns (imgs, targets, shapes, masks): shapes[i] = ((h0, w0), ((h / h0, w / w0), (dw, dh))) as :151."""
     dev = images[0].device
     B = len(ids)
@@ -615,7 +620,11 @@ def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, nor
         labs.append(res)
         polys.extend(sgs)
         inst.extend([b] * len(sgs))
-    out = _render(jobs, B, s, dev, dtype, normalize)
+    if area:
+        out = letterbox_area_batch([images[i] for i in ids], [(j.rh[0], j.rw[0]) for j in jobs], [(j.y1a[0], j.x1a[0]) for j in jobs], s, s, dtype,
+                                   normalize)
+    else:
+        out = _render(jobs, B, s, dev, dtype, normalize)
     masks, order = polygon_masks(polys, inst, B, s, s, mask_ratio, overlap, None, dev)
     if overlap:
         labs = _reorder(labs, order)
@@ -625,13 +634,14 @@ def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, nor
 
 class SegValLoader:
     """Validation loader of a segmentation dataset (augment = False, rect = False): yields the (imgs, targets, paths, shapes, masks)
-    five-tuple `segment_val.run` consumes, images in dataset order."""
+    five-tuple `segment_val.run` consumes, images in dataset order.  area: see `seg_letterbox_batch`."""
 
-    def __init__(self, images, labels, segments, img_size=640, batch_size=16, dtype=torch.uint8, paths=None, overlap=True, mask_ratio=1, classes=None):
+    def __init__(self, images, labels, segments, img_size=640, batch_size=16, dtype=torch.uint8, paths=None, overlap=True, mask_ratio=1, classes=None,
+                 area=False):
         if labels is None:
             labels = [labels_from_segments(c, sg) for c, sg in zip(classes, segments)]
         self.images, self.labels, self.segments, self.s, self.bs = images, labels, segments, img_size, batch_size
-        self.dtype, self.overlap, self.mask_ratio = dtype, overlap, mask_ratio
+        self.dtype, self.overlap, self.mask_ratio, self.area = dtype, overlap, mask_ratio, area
         self.paths = paths or [f"image{i}" for i in range(len(images))]
 
     def __len__(self):
@@ -641,8 +651,195 @@ class SegValLoader:
         for b0 in range(0, len(self.images), self.bs):
             ids = list(range(b0, min(b0 + self.bs, len(self.images))))
             imgs, targets, shapes, masks = seg_letterbox_batch(self.images, self.labels, self.segments, ids, self.s, self.dtype, normalize=True,
-                                                               overlap=self.overlap, mask_ratio=self.mask_ratio)
+                                                               overlap=self.overlap, mask_ratio=self.mask_ratio, area=self.area)
             yield imgs, targets, [self.paths[i] for i in ids], shapes, masks
+
+
+# ---- detection validation: LoadImagesAndLabels(augment=False, rect, pad) (utils/dataloaders.py:589-612, :710-736, :768-790) -----------------
+@functools.lru_cache(maxsize=256)
+def _area_axis(ssize, dsize):
+    """One axis of OpenCV's `computeResizeAreaTab` (modules/imgproc/src/resize.cpp) in double, as include/yolov5_hip.h states it:
+    -> (entries (dsize, 2) int32 {first source index, tap count}, weights float32 in entry order).  The taps of an output index are
+    consecutive source indices: the left partial cell, the full cells, the right partial cell."""
+    scale = float(ssize) / dsize
+    ents, wts = np.empty((dsize, 2), np.int32), []
+    for d in range(dsize):
+        f1 = d * scale
+        f2 = f1 + scale
+        cell = min(scale, ssize - f1)
+        s1, s2 = math.ceil(f1), min(math.floor(f2), ssize - 1)
+        s1 = min(s1, s2)
+        w = []
+        first = s1
+        if s1 - f1 > 1e-3:
+            first = s1 - 1
+            w.append((s1 - f1) / cell)
+        w.extend([1.0 / cell] * (s2 - s1))
+        if f2 - s2 > 1e-3:
+            w.append(min(min(f2 - s2, 1.0), cell) / cell)
+        ents[d] = first, len(w)
+        wts.extend(w)
+    return ents, np.asarray(wts, dtype=np.float64).astype(np.float32)
+
+
+def _int_scale(ssize, dsize):
+    """The integer k when (double)ssize / dsize is within DBL_EPSILON of it (cv::resize's `is_area_fast` test), else 0."""
+    scale = float(ssize) / dsize
+    k = int(round(scale))
+    return k if abs(scale - k) < np.finfo(np.float64).eps else 0
+
+
+def area_jobs(ims, sizes, places):
+    """Job table and tap tables of one `y5_letterbox_area_batch` launch.  ims: uint8 (h0, w0, 3) tensors; sizes[i] = (nh, nw) of the resized
+    image (load_image); places[i] = (top, left) of it on the canvas.  The path per job: copy when the sizes agree, INTER_LINEAR when either side
+    grows, else INTER_AREA -- 2x2, integer block or tap tables.  -> (ctypes array of y5_area_job, int32 words)."""
+    jobs = (_lib.AreaJob * len(ims))()
+    words, off, seen = [], 0, {}
+    for j, im, (nh, nw), (top, left) in zip(jobs, ims, sizes, places):
+        if not (_lib.accepts(im) and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
+            raise ValueError("letterbox_area_batch: images must be uint8 (h, w, 3) device tensors with contiguous rows")
+        h0, w0 = int(im.shape[0]), int(im.shape[1])
+        j.src, j.h0, j.w0, j.stride = im.data_ptr(), h0, w0, int(im.stride(0))
+        j.nh, j.nw, j.top, j.left = int(nh), int(nw), int(top), int(left)
+        if (nh, nw) == (h0, w0):
+            j.mode = _lib.AREA_COPY
+        elif nh > h0 or nw > w0:
+            j.mode = _lib.AREA_LINEAR
+        else:
+            ix, iy = _int_scale(w0, nw), _int_scale(h0, nh)
+            if ix == 2 and iy == 2:
+                j.mode = _lib.AREA_2X2
+            elif ix and iy:
+                j.mode, j.ix, j.iy = _lib.AREA_INT, ix, iy
+            else:
+                j.mode = _lib.AREA_TAB
+                key = (h0, w0, int(nh), int(nw))
+                if key not in seen:                              # {first, count, weight offset} per output index, then the weights, x then y
+                    tabs = []
+                    for ssize, dsize in ((w0, nw), (h0, nh)):
+                        ents, wts = _area_axis(ssize, int(dsize))
+                        e = np.empty((len(ents), 3), np.int32)
+                        e[:, :2] = ents
+                        e[:, 2] = off + 3 * len(ents) + np.concatenate(([0], np.cumsum(ents[:-1, 1])))
+                        tabs.append(off)
+                        words += [e.reshape(-1), wts.view(np.int32)]
+                        off += 3 * len(ents) + len(wts)
+                    seen[key] = tabs
+                j.xtab, j.ytab = seen[key]
+    return jobs, (np.concatenate(words) if words else np.zeros(0, np.int32))
+
+
+def letterbox_area_batch(ims, sizes, places, H, W, dtype=torch.uint8, normalize=False, pad_value=114):
+    """`load_image` + the padding of `letterbox` + HWC -> CHW, BGR -> RGB (+ `/ 255`) for a ragged batch in ONE launch (csrc/val_data.h).
+    Arguments as `area_jobs`; -> (B, 3, H, W) `dtype`."""
+    dev = ims[0].device
+    B = len(ims)
+    for im, (nh, nw), (top, left) in zip(ims, sizes, places):
+        if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > H or left + nw > W:
+            raise ValueError(f"letterbox_area_batch: a {nh} x {nw} image at ({top}, {left}) does not fit the {H} x {W} canvas")
+    jobs, tabs = area_jobs(ims, sizes, places)
+    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev)
+    tabs_d = torch.from_numpy(tabs).to(dev) if len(tabs) else None
+    out = torch.empty((B, 3, H, W), dtype=dtype, device=dev)
+    code = {torch.uint8: _lib.Y5_U8, torch.float16: _lib.Y5_F16, torch.float32: _lib.Y5_F32}[dtype]
+    lib = _lib.lib()
+    _lib.check(lib.y5_letterbox_area_batch(C.c_void_p(table.data_ptr()), C.c_void_p(tabs_d.data_ptr()) if tabs_d is not None else None, len(tabs),
+                                           B, H, W, int(pad_value), C.c_void_p(out.data_ptr()), code, int(normalize and dtype != torch.uint8),
+                                           _lib.stream(dev)), lib)
+    return out
+
+
+def _xywhn2xyxy(x, w, h, padw, padh):
+    """ultralytics.utils.ops.xywhn2xyxy (call site utils/dataloaders.py:721), the reference's expressions: the TYPES of w, h, padw, padh decide
+    whether numpy evaluates them in float32 or float64, so the caller passes scalars made the way `letterbox` makes them."""
+    y = x.copy()
+    y[..., 0] = w * (x[..., 0] - x[..., 2] / 2) + padw
+    y[..., 1] = h * (x[..., 1] - x[..., 3] / 2) + padh
+    y[..., 2] = w * (x[..., 0] + x[..., 2] / 2) + padw
+    y[..., 3] = h * (x[..., 1] + x[..., 3] / 2) + padh
+    return y
+
+
+class ValLoader:
+    """Validation loader of a detection dataset over frames resident on the device: `LoadImagesAndLabels(augment=False, rect=rect, pad=pad)` +
+    `collate_fn` as val.py:228-237 builds it (rect=True, pad=0.5; `--task speed`: rect=False, pad=0.0).  rect sorts the images by aspect ratio
+    h / w with the reference's own `argsort` call and gives every batch the smallest stride-multiple canvas that holds its images
+    (:589-612); each batch is ONE `y5_letterbox_area_batch` launch on that (H, W): load_image's resize -- INTER_AREA when the image shrinks,
+    INTER_LINEAR when it grows -- and the padding of letterbox(auto=False, scaleup=False), which for these shapes never resizes again
+    (asserted).  Yields (imgs, targets, paths, shapes) as `val_loop.run` and `train_loop.train(val_loader=...)` consume them; re-iterable.
+    `.shapes` (w, h) and `.labels` are in the sorted order, `.order[k]` is the dataset index of position k, `.batch[k]` its batch,
+    `.batch_shapes[b]` the (H, W) of batch b (rect only).  A rect run makes the model build one plan per distinct (B, H, W)."""
+
+    def __init__(self, images, labels, img_size=640, batch_size=32, stride=32, pad=0.5, rect=True, dtype=torch.uint8, paths=None, single_cls=False):
+        n = len(images)
+        self.images, self.img_size, self.bs, self.stride, self.pad, self.rect, self.dtype = list(images), img_size, batch_size, stride, pad, rect, dtype
+        self.paths = list(paths) if paths else [f"image{i}" for i in range(n)]
+        self.labels = [np.array(lb, dtype=np.float32).reshape(-1, 5).copy() for lb in labels]
+        if single_cls:                                                      # :586-587
+            for lb in self.labels:
+                lb[:, 0] = 0
+        self.shapes = np.array([[int(im.shape[1]), int(im.shape[0])] for im in images])   # wh, as the label cache holds them (:551)
+        bi = np.floor(np.arange(n) / batch_size).astype(int)               # :567-569
+        nb = bi[-1] + 1
+        self.batch, self.order = bi, np.arange(n)
+        if rect:                                                            # :589-612
+            s = self.shapes
+            ar = s[:, 1] / s[:, 0]
+            irect = ar.argsort()
+            self.order = irect
+            self.images, self.paths = [self.images[i] for i in irect], [self.paths[i] for i in irect]
+            self.labels = [self.labels[i] for i in irect]
+            self.shapes = s[irect]
+            ar = ar[irect]
+            shapes = [[1, 1]] * nb
+            for i in range(nb):
+                ari = ar[bi == i]
+                mini, maxi = ari.min(), ari.max()
+                if maxi < 1:
+                    shapes[i] = [maxi, 1]
+                elif mini > 1:
+                    shapes[i] = [1, 1 / mini]
+            self.batch_shapes = np.ceil(np.array(shapes) * img_size / stride + pad).astype(int) * stride
+
+    def __len__(self):
+        return (len(self.images) + self.bs - 1) // self.bs
+
+    def _item(self, k):
+        """:712-736 for sorted position k, without the pixels -> ((nh, nw), (top, left), labels (k, 5) normalised xywh, shapes entry)."""
+        im = self.images[k]
+        h0, w0 = int(im.shape[0]), int(im.shape[1])
+        h, w = _resized_hw(h0, w0, self.img_size)                           # load_image :784-788
+        shape = self.batch_shapes[self.batch[k]] if self.rect else self.img_size
+        new_shape = (shape, shape) if isinstance(shape, int) else shape     # letterbox(im, shape, auto=False, scaleup=False), augmentations.py:87-108
+        r = min(new_shape[0] / h, new_shape[1] / w)
+        r = min(r, 1.0)
+        new_unpad = round(w * r), round(h * r)
+        dw, dh = new_shape[1] - new_unpad[0], new_shape[0] - new_unpad[1]
+        dw /= 2
+        dh /= 2
+        if (w, h) != new_unpad:
+            raise AssertionError(f"ValLoader: image {self.paths[k]} ({h} x {w} after load_image) needs a second resize to fit {tuple(new_shape)}")
+        top, left = round(dh - 0.1), round(dw - 0.1)
+        lb = self.labels[k].copy()
+        if lb.size:
+            lb[:, 1:] = _xywhn2xyxy(lb[:, 1:], r * w, r * h, dw, dh)        # :721
+        H, W = int(new_shape[0]), int(new_shape[1])
+        lb = _finish_labels(lb, {"flipud": False, "fliplr": False}, W, H)   # :736 xyxy2xywhn(clip=True, eps=1e-3) -> (k, 6)
+        return (h, w), (top, left), lb, ((h0, w0), ((h / h0, w / w0), (dw, dh))), (H, W)
+
+    def __iter__(self):
+        n = len(self.images)
+        for b0 in range(0, n, self.bs):
+            ks = list(range(b0, min(b0 + self.bs, n)))
+            items = [self._item(k) for k in ks]
+            H, W = items[0][4]
+            imgs = letterbox_area_batch([self.images[k] for k in ks], [it[0] for it in items], [it[1] for it in items], H, W, self.dtype,
+                                        normalize=True)
+            labs = []
+            for i, it in enumerate(items):
+                it[2][:, 0] = i                                             # collate_fn :860-862
+                labs.append(it[2])
+            yield imgs, torch.from_numpy(np.concatenate(labs, 0)), [self.paths[k] for k in ks], [it[3] for it in items]
 
 
 # ---- classification (utils/dataloaders.py:949-1013, the augment=False branch) -------------------------------------------------------------

@@ -7,6 +7,8 @@ Device side (one HIP launch per batch, `csrc/metrics.hip` -> `y5_val_match`):
     ValStats                                            the `stats` list of val.py:218,308 kept on the device
     match_masks_batch(out, counts, protos, targets,     segment/val.py:287-308 mask matching for all images of a batch, the predicted
                       masks, iouv, overlap, shape)      masks computed from the prototypes inside the matcher (never written)
+    ConfusionMatrix                                     utils/metrics.py:129-183 as an int32 device accumulator: `update` = one
+                                                        `y5_val_confusion` launch per batch, `.matrix` = one D2H copy on read
 Host side -- numpy, as in the reference (SURVEY keeps `ap_per_class` on the CPU: it runs once per epoch on a few
 thousand rows): `ap_per_class`, `compute_ap`, `smooth`, `fitness`.
 """
@@ -181,6 +183,79 @@ class ValStats:
             res.update(mp=float(p.mean()), mr=float(r.mean()), map50=float(ap[:, 0].mean()), map=float(ap.mean()), ap=ap, ap_class=ap_class)
         res["nt"] = np.bincount(tcls.astype(int), minlength=nc or 0)
         return res
+
+
+class ConfusionMatrix:
+    """utils/metrics.py:129-183 on the device.  The counts live in one (nc + 1, nc + 1) int32 tensor that `y5_val_confusion` adds to with
+    integer atomics -- no `.cpu().numpy()` round trip and no Python loop per image (val.py:293,309), no host synchronisation until `.matrix` is
+    read.  Rows are predicted classes, columns true classes, index nc is the background.  Semantics (strict `conf > self.conf` and
+    `iou > iou_thres`, the two-stage matching, the `if n:` gate of the false positives) are stated at include/yolov5_hip.h; two pairs of equal
+    IoU, whose order the reference leaves to argsort, go to the lower index.  `single_cls` is the caller's business, as in val_loop."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45):
+        self.nc, self.conf, self.iou_thres = int(nc), conf, iou_thres
+        self._counts = None
+
+    def _acc(self, dev):
+        if self._counts is None:
+            self._counts = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int32, device=dev)
+        return self._counts
+
+    @property
+    def matrix(self):
+        """(nc + 1, nc + 1) float64 numpy array, as the reference keeps it: one device-to-host copy."""
+        if self._counts is None:
+            return np.zeros((self.nc + 1, self.nc + 1))
+        return self._counts.cpu().numpy().astype(np.float64)
+
+    def _launch(self, det, counts, bs, lab, img_col, cls_col, box_col, xywh, sc, dev):
+        lib = _lib.lib()
+        max_det = det.shape[1] if det is not None else 0
+        rc = lib.y5_val_confusion(_p(det), det.shape[2] if det is not None else 0, max_det, _p(counts), bs, _p(lab) if lab.numel() else None,
+                                  lab.shape[1], lab.shape[0], img_col, cls_col, box_col, xywh, _p(sc), float(self.conf), float(self.iou_thres),
+                                  self.nc, _p(self._acc(dev)), _lib.stream(dev))
+        _lib.check(rc, lib)
+
+    def process_batch(self, detections, labels):
+        """The reference's signature for ONE image: detections (N, 6) [x1, y1, x2, y2, conf, cls] or None, labels (M, 5) [cls, x1, y1, x2, y2]
+        (with detections=None: the (M) class vector, val.py:293), both in one pixel space."""
+        _need_gpu(labels, "ConfusionMatrix.process_batch")
+        dev = labels.device
+        if detections is None:
+            lab = torch.zeros((labels.numel(), 5), dtype=torch.float32, device=dev)
+            lab[:, 0] = labels.reshape(-1).float()
+            return self._launch(None, None, 1, lab, -1, 0, 1, 0, None, dev)
+        if detections.shape[0] > 1024:
+            raise ValueError("ConfusionMatrix.process_batch: at most 1024 detections per image")
+        lab = labels.float().contiguous()
+        if detections.shape[0] == 0:
+            return self._launch(None, None, 1, lab, -1, 0, 1, 0, None, dev)
+        self._launch(detections.float().contiguous()[None], None, 1, lab, -1, 0, 1, 0, None, dev)
+
+    def update(self, out, counts, targets, shapes=None):
+        """val.py:289-309 for a whole batch in one launch; arguments as `match_batch`: the padded NMS result, targets (M, 6) [img, cls, cx, cy, w, h] in
+        letterboxed pixels, the loader's `shapes` or None.  An image without detections sends its labels to the background row; an image
+        without labels adds nothing."""
+        _need_gpu(out, "ConfusionMatrix.update")
+        bs, max_det, _ = out.shape
+        dev = out.device
+        if out.dtype != torch.float32 or not out.is_contiguous():
+            out = out.float().contiguous()
+        tg = targets.to(device=dev, dtype=torch.float32).contiguous()
+        sc = None
+        if shapes is not None:
+            sc = torch.tensor([[rp[0][0], rp[1][0], rp[1][1], s0[0], s0[1]] for s0, rp in shapes], dtype=torch.float32).to(dev, non_blocking=True)
+        cn = counts.to(device=dev, dtype=torch.int32) if counts is not None else None
+        self._launch(out, cn, bs, tg, 0, 1, 2, 1, sc, dev)
+
+    def plot(self, normalize=True, save_dir="", names=()):
+        raise NotImplementedError("ConfusionMatrix.plot: the seaborn heat map is outside the hot path")
+
+    def print(self):
+        """utils/metrics.py:218-221."""
+        m = self.matrix
+        for i in range(self.nc + 1):
+            print(" ".join(map(str, m[i])))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The reference's validation loop, composed from the yolov5_amd seams (val.py:202-218 set-up, :255-333 batch loop and metrics, :390-396 return
 value) -- what train.py calls once per epoch on the EMA model (train.py:440-455) and what `val.py` runs stand-alone.  Not the CLI: no dataset
-yaml, plots, txt / json export, confusion matrix or callbacks; the numbers the caller gets back are the reference's
+yaml, plots, txt / json export or callbacks (the confusion matrix of val.py:243,293,309 is filled when the caller passes one); the numbers the caller gets back are the reference's
 
     (mp, mr, map50, map, box_loss, obj_loss, cls_loss), maps, (pre-process, inference, NMS ms per image)
 
@@ -26,7 +26,7 @@ def _sync(device):
 
 
 def run(model, dataloader, conf_thres=0.001, iou_thres=0.6, max_det=300, half=True, single_cls=False, compute_loss=None, nc=None,
-        training=True, profile=False):
+        training=True, profile=False, confusion_matrix=None):
     """val.py:run for a model that is already on the device.
 
     dataloader yields (im uint8|float BCHW, targets (M, 6) [img, cls, x, y, w, h] normalised, paths, shapes) with shapes[i] =
@@ -34,7 +34,8 @@ def run(model, dataloader, conf_thres=0.001, iou_thres=0.6, max_det=300, half=Tr
     letterboxed frame).  `half`: the model is converted IN PLACE for the run and back to float afterwards, exactly as val.py:187,388 do to the
     EMA model train.py passes in (its weights therefore pick up one fp16 rounding per validation -- reference behaviour, kept).
     `profile=True` synchronises around the three phases to fill the per-image times (val.py's `Profile`); off, the loop never blocks the host
-    between batches and the times are the wall clock of the whole run split by enqueue time."""
+    between batches and the times are the wall clock of the whole run split by enqueue time.
+    confusion_matrix: a `metrics.ConfusionMatrix` to fill (val.py's `plots` gate, :293,309): one more launch per batch; None changes nothing."""
     device = next(model.parameters()).device
     was_training = model.training
     model.half() if half else model.float()                                   # val.py:187
@@ -69,6 +70,8 @@ def run(model, dataloader, conf_thres=0.001, iou_thres=0.6, max_det=300, half=Tr
         if single_cls:
             det_out[..., 5] = 0                                               # :282
         stats.update(det_out, cnt, targets, shapes)                           # :266-309 for the whole batch in one launch
+        if confusion_matrix is not None:
+            confusion_matrix.update(det_out, cnt, targets, shapes)            # :293,309
         if profile:
             _sync(device)
         t3 = time.perf_counter()
