@@ -824,6 +824,26 @@ int y5_mt_grad_norm(const y5_mt_tensor* table_dev, int ntensors, long long max_n
 int y5_mt_sgd_step(const y5_mt_tensor* table_dev, int ntensors, long long max_numel, const float* lr4, const float* wd4, float momentum,
                    int nesterov, float inv_scale, const float* stats_dev, float ema_decay, void* stream);
 int y5_mt_lerp(const y5_mt_tensor* table_dev, int ntensors, long long max_numel, float decay, void* stream);
+/* The other optimizers of utils/torch_utils.py:257-290 (`torch.optim.Adam(betas=(momentum, 0.999))`, `AdamW(weight_decay=0.0)`,
+ * `RMSprop(momentum=momentum)`; classify/train.py:176 defaults to Adam) behind the same train.py:413-421 sequence, in torch's single-tensor
+ * order (torch/optim/adam.py `_single_tensor_adam`, rmsprop.py `_single_tensor_rmsprop`), every product and sum rounded separately in fp32:
+ *   y5_mt_adam_step    : d = grad * inv_scale * stats[1]; adamw ? p *= 1 - lr * wd : d += wd * p; m += (d - m) * (1 - beta1);
+ *                        v = v * beta2 + (1 - beta2) * d * d; p += -(lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ *   y5_mt_rmsprop_step : d as above; d += wd * p; v = v * alpha + (1 - alpha) * d * d; avg = sqrt(v) + eps;
+ *                        mom ? (buf = buf * momentum + d / avg; p -= lr * buf) : p += -lr * (d / avg)       (centered=False)
+ * table row: mom = exp_avg / momentum_buffer (NULL: RMSProp without momentum); second_dev[row] = exp_avg_sq / square_avg, a DEVICE array of
+ * ntensors fp32 pointers parallel to the table (y5_mt_tensor itself is unchanged).  Zero-initialised states give torch's first step.
+ * step_dev: the optimizer's step count t, ONE fp32 scalar on the device.  A one-thread kernel in front of the update adds 1 to it unless
+ * stats[2] != 0 and derives 1 - beta^t, lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double, each rounded once to float, into rec_dev
+ * (8 floats of device scratch); nothing about the count is read by the host.  stats == NULL: no clipping, the count always advances.
+ * stats[2] != 0: parameters, both states and the count are left untouched, the EMA still moves.  lr4 / wd4 / betas / eps are doubles as
+ * torch holds them.  16-byte accesses where every pointer of a row is 16-byte aligned, 4-byte ones otherwise: same bits either way. */
+int y5_mt_adam_step(const y5_mt_tensor* table_dev, void* const* second_dev, int ntensors, long long max_numel, const double* lr4,
+                    const double* wd4, double beta1, double beta2, double eps, int adamw, float inv_scale, const float* stats_dev,
+                    float ema_decay, float* step_dev, float* rec_dev /* 8 floats */, void* stream);
+int y5_mt_rmsprop_step(const y5_mt_tensor* table_dev, void* const* second_dev, int ntensors, long long max_numel, const double* lr4,
+                       const double* wd4, double alpha, double eps, double momentum, float inv_scale, const float* stats_dev,
+                       float ema_decay, float* step_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * AutoAnchor (utils/autoanchor.py) -- csrc/autoanchor.h.  `wh` / `obs` are (n, 2) fp32 device rows; every reduction is deterministic

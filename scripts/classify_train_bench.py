@@ -1,9 +1,11 @@
 """Measures classification training on one MI355X: yolov5s-cls shape (ClassificationModel of yolov5s, nc = 1000), batch 128, 224 x 224, fp16.
 
-    python scripts/classify_train_bench.py [--out profiles/classify/classify_train_bench.json]
+    python scripts/classify_train_bench.py [--optimizer SGD|Adam|AdamW|RMSProp] [--fused] [--out profiles/classify/classify_train_bench.json]
 
 Prints (and writes as json) four things, each timed with device events after a warm-up over a window of at least half a second:
-  * the whole step: train-mode forward, loss, backward, HipSGD.step_fused (unscale + clip + update) -- images/s;
+  * the whole step: train-mode forward, loss, backward and the optimizer block (unscale + clip + update) -- images/s.  --optimizer SGD (default):
+    HipSGD.step_fused; another name: the torch optimizer through train_loop.host_amp_step as classify_train.train runs it by default (Adam is that
+    loop's default optimizer), or with --fused the HipAdam / HipAdamW / HipRMSprop step_fused;
   * y5_classify_head_bwd alone (Dropout 0 and 0.2);
   * y5_classify_ce_bwd alone;
   * the torch autograd composition of pool + dropout + linear + cross-entropy (forward and backward) on the same tensors in the same process,
@@ -22,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from yolov5_amd import _lib  # noqa: E402
 from yolov5_amd.torch_utils import classify_ce_bwd, smart_optimizer, smartCrossEntropyLoss  # noqa: E402
+from yolov5_amd.train_loop import LossScaler, host_amp_step  # noqa: E402
 from yolov5_amd.yolo import ClassificationModel, DetectionModel  # noqa: E402
 
 
@@ -48,14 +51,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--imgsz", type=int, default=224)
+    ap.add_argument("--optimizer", default="SGD", choices=["SGD", "Adam", "AdamW", "RMSProp"])
+    ap.add_argument("--fused", action="store_true", help="smart_optimizer(fused=True): the device path for Adam / AdamW / RMSProp")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     dev = torch.device("cuda")
     B, S, nc = a.batch, a.imgsz, 1000
-    res = {"batch": B, "imgsz": S, "nc": nc, "dtype": "fp16", "device": torch.cuda.get_device_name(0)}
+    res = {"batch": B, "imgsz": S, "nc": nc, "dtype": "fp16", "device": torch.cuda.get_device_name(0), "optimizer": a.optimizer, "fused": bool(a.fused)}
 
     model = ClassificationModel(model=DetectionModel("yolov5s.yaml"), nc=nc, cutoff=10).to(dev).train()
-    optimizer = smart_optimizer(model, "SGD", 0.001, momentum=0.9, decay=5e-5)
+    optimizer = smart_optimizer(model, a.optimizer, 0.001, momentum=0.9, decay=5e-5, fused=a.fused)
+    res["optimizer_class"] = type(optimizer).__module__ + "." + type(optimizer).__name__
+    scaler = LossScaler(enabled=True, init_scale=1024.0, growth_interval=10 ** 9)   # (host path only: a fixed scale, as below)
+    params = list(model.parameters())
     criterion = smartCrossEntropyLoss(0.1)
     x = torch.rand(B, 3, S, S, device=dev).half()
     labels = torch.randint(0, nc, (B,), device=dev)
@@ -64,7 +72,11 @@ def main():
     def step():
         loss = criterion(model(x), labels)
         (loss * scale).backward()
-        optimizer.step_fused(inv_scale=1.0 / scale, max_norm=10.0)
+        if hasattr(optimizer, "step_fused"):
+            optimizer.step_fused(inv_scale=1.0 / scale, max_norm=10.0)
+        else:
+            host_amp_step(optimizer, params, scaler, 10.0)
+            scaler.update()
         optimizer.zero_grad()
 
     ms = timed(step)

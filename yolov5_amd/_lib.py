@@ -163,6 +163,10 @@ EXPORTS = {
     "y5_mt_sgd_step": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_float,
                                  C.c_void_p, C.c_float, C.c_void_p]),
     "y5_mt_lerp": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
+    "y5_mt_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
+                                  C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y5_mt_rmsprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
+                                     C.c_double, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "y5_conv2d_wgrad": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "y5_conv2d_wgrad_det": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y5_conv2d_wgrad_ws_bytes": (C.c_longlong, [C.POINTER(ConvDesc), C.c_int]),

@@ -50,7 +50,8 @@ def reference_class_paths():
 
 
 def save_checkpoint(path, model, ema=None, optimizer=None, epoch=-1, best_fitness=None, opt=None, reference_paths=True):
-    """train.py:469-488: model / EMA as fp16 deep copies, optimizer state_dict (HipSGD keeps torch.optim.SGD's layout), bookkeeping."""
+    """train.py:469-488: model / EMA as fp16 deep copies, optimizer state_dict (HipSGD / HipAdam / HipAdamW / HipRMSprop keep the layout of
+    the torch.optim class of the same name, `step` as one host tensor per parameter), bookkeeping."""
     ckpt = {
         "epoch": epoch,
         "best_fitness": best_fitness,

@@ -2,8 +2,9 @@
 
 MI355X mapping: the train-mode forward and the backward are the TrainEngine plan (the Classify head's pool + Dropout + Linear and its backward:
 csrc/classify_train.h), the loss is y5_classify_post with y5_classify_ce_bwd as its gradient, the optimizer block is HipSGD.step_fused for SGD
-(unscale + clip + step + EMA in three launches) and train_loop.host_amp_step for the torch optimizers (Adam is the reference's default here; a
-fused Adam step is not built), validation is classify_val.run on the EMA model.
+(unscale + clip + step + EMA in three launches) and train_loop.host_amp_step for the torch optimizers (Adam is the reference's default here);
+fused_optimizer=True puts Adam / AdamW / RMSProp on the same device path (torch_utils.HipAdam / HipAdamW / HipRMSprop: four launches, the step count
+and the overflow flag stay on the device).  Validation is classify_val.run on the EMA model.
 
 Not here: warm-up and gradient accumulation (the reference's classification loop has neither), classify_albumentations(augment=True) (without
 albumentations the reference trains on torch_transforms as well: dataloaders.ClassificationLoader), image folders, torchvision models, plots,
@@ -21,11 +22,11 @@ from .train_loop import LossScaler, host_amp_step, lr_lambda
 
 
 def train(model, trainloader, testloader=None, epochs=10, optimizer_name="Adam", lr0=0.001, decay=5e-5, label_smoothing=0.1, dropout=None, amp=True,
-          ema=True, max_norm=10.0, pretrained=True, save_dir=None, on_batch_end=None):
+          ema=True, max_norm=10.0, pretrained=True, save_dir=None, on_batch_end=None, fused_optimizer=False):
     """Runs `epochs` epochs over `trainloader` (re-iterable of (images (b, 3, s, s) float, labels (b)) batches on the model's device).  amp: fp16
     images select the fp16 plan and the loss is scaled (GradScaler's policy: train_loop.LossScaler); amp=False feeds fp32 images to the fp32 plan.
     testloader: validated once per epoch with the EMA model (the live model without an EMA), fitness = top-1 accuracy.  save_dir: last.pt / best.pt
-    as classify/train.py:271-289 writes them (the fp16 copy of the EMA as "model", no optimizer state).
+    as classify/train.py:271-289 writes them (the fp16 copy of the EMA as "model", no optimizer state).  fused_optimizer: smart_optimizer(fused=True).
     Returns dict(model, ema, optimizer, scheduler, scaler, losses (iterations,), tloss / vloss / top1 / top5 / lr per epoch, best_fitness)."""
     for m in model.modules():                                                       # :154-158
         if not pretrained and hasattr(m, "reset_parameters"):
@@ -34,7 +35,7 @@ def train(model, trainloader, testloader=None, epochs=10, optimizer_name="Adam",
             m.p = dropout
     for p in model.parameters():
         p.requires_grad = True                                                      # :159-160
-    optimizer = smart_optimizer(model, optimizer_name, lr0, momentum=0.9, decay=decay)   # :176
+    optimizer = smart_optimizer(model, optimizer_name, lr0, momentum=0.9, decay=decay, fused=fused_optimizer)   # :176
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda=lr_lambda(epochs, 0.01))   # :179-186 (linear, lrf = 0.01)
     ema_obj = ModelEMA(model) if ema else None                                      # :191
     criterion = smartCrossEntropyLoss(label_smoothing=label_smoothing)              # :199

@@ -16,6 +16,7 @@
 
 namespace {
 constexpr int CH = 16384;  // elements per workgroup: 256 threads x 16 float4
+constexpr int CHV = 16384; // elements per workgroup of the Adam / RMSProp update: 256 threads x 16 x 16 bytes per stream (2048 ... 16384 measured: the same)
 
 struct MtStats { float total_norm, clip_coef, found_inf, pad; };
 }  // namespace
@@ -122,6 +123,160 @@ void y5_mt_sgd_kernel(const y5_mt_tensor* __restrict__ tab, const MtStats* __res
   }
 }
 
+// ---- Adam / AdamW / RMSProp (torch/optim/adam.py _single_tensor_adam, rmsprop.py _single_tensor_rmsprop; the other choices of
+// utils/torch_utils.py:257-290).  Same table, grid and stats contract as the SGD kernel; the second state tensor (exp_avg_sq /
+// square_avg) comes as a parallel device array of pointers, one per table row.  The step count lives on the device: GradScaler.step skips
+// optimizer.step() on overflow, so the count -- and the bias corrections that depend on it -- may only advance when the update is taken.
+struct MtStepRec { float step_size[4]; float bc2_sqrt; float pad[3]; };  // lr[g] / (1 - b1^t) and sqrt(1 - b2^t), each rounded once from double
+struct MtStepArgs { double lr[4]; double b1, b2; int bias, use_stats; };
+
+// one thread in front of the update: advance the count (unless the step is skipped) and derive what depends on it
+__global__ void y5_mt_step_prep_kernel(float* __restrict__ step, MtStepRec* __restrict__ rec, const MtStats* __restrict__ stats, const MtStepArgs a) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (a.use_stats && stats->found_inf != 0.f) return;
+  const float t = *step + 1.0f;
+  *step = t;
+  if (!a.bias) return;
+  const double bc1 = 1.0 - pow(a.b1, (double)t), bc2 = 1.0 - pow(a.b2, (double)t);  // torch: Python floats, i.e. doubles, on the host
+  for (int g = 0; g < 4; ++g) rec->step_size[g] = (float)(a.lr[g] / bc1);
+  rec->bc2_sqrt = (float)sqrt(bc2);
+}
+
+struct MtAdamHyper {
+  float wd[4];     // Adam: grad += wd * w
+  float decay[4];  // AdamW: w *= 1 - lr * wd
+  float b2, one_minus_b1, one_minus_b2, eps, inv_scale, ema_d;
+  int adamw, use_stats;
+};
+struct MtRmsHyper {
+  float lr[4], wd[4];
+  float alpha, one_minus_alpha, eps, mu, inv_scale, ema_d;
+  int use_stats;
+};
+
+// One element of either path (16-byte or scalar accesses): the SAME code, so both give the same bits.
+struct MtAdamOp {
+  float coef, inv_scale, wd, decay, b2, omb1, omb2, eps, neg_step, bc2s;
+  int adamw;
+  __device__ __forceinline__ void operator()(float& w, float d, float& m, float& v) const {
+    if (inv_scale != 1.0f) d = d * inv_scale;
+    if (coef != 1.0f) d = d * coef;
+    if (adamw) w = w * decay;
+    else if (wd != 0.f) d = d + wd * w;
+    m = m + (d - m) * omb1;                  // exp_avg.lerp_(grad, 1 - beta1)
+    v = v * b2 + omb2 * d * d;               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    const float denom = sqrtf(v) / bc2s + eps;
+    w = w + neg_step * (m / denom);          // param.addcdiv_(exp_avg, denom, value=-step_size)
+  }
+};
+struct MtRmsOp {
+  float coef, inv_scale, wd, lr, alpha, oma, eps, mu;
+  bool has_buf;
+  __device__ __forceinline__ void operator()(float& w, float d, float& buf, float& v) const {
+    if (inv_scale != 1.0f) d = d * inv_scale;
+    if (coef != 1.0f) d = d * coef;
+    if (wd != 0.f) d = d + wd * w;
+    v = v * alpha + oma * d * d;             // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    const float avg = sqrtf(v) + eps;
+    if (has_buf) {
+      buf = buf * mu + d / avg;              // buf.mul_(momentum).addcdiv_(grad, avg)
+      w = w - lr * buf;
+    } else {
+      w = w + (-lr) * (d / avg);             // param.addcdiv_(grad, avg, value=-lr)
+    }
+  }
+};
+
+// One CH-element chunk of one row: 16-byte accesses when every pointer of the row is 16-byte aligned (chunk starts are multiples of CH,
+// so the row's alignment is the chunk's), scalar accesses otherwise and for the last n % 4 elements.  skip: only the EMA moves.
+template <class Op>
+__device__ __forceinline__ void mt_update_chunk(const y5_mt_tensor& t, float* __restrict__ v, long long base, bool skip, float ema_d, const Op& op) {
+  const long long end = base + CHV < t.n ? base + CHV : t.n;
+  float* p = static_cast<float*>(t.param);
+  const float* g = static_cast<const float*>(t.grad);
+  float* m = static_cast<float*>(t.mom);
+  float* e = static_cast<float*>(t.ema);
+  const float omd = 1.0f - ema_d;
+  const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e;  // a null pointer adds nothing
+  long long done = base;
+  if ((bits & 15) == 0) {
+    const long long nvec = (end - base) >> 2;
+    for (long long k = threadIdx.x; k < nvec; k += 256) {
+      const long long j = base + 4 * k;
+      float4_t w4 = *reinterpret_cast<const float4_t*>(p + j);
+      float4_t e4 = {0.f, 0.f, 0.f, 0.f};
+      if (e) e4 = *reinterpret_cast<const float4_t*>(e + j);
+      if (!skip) {
+        const float4_t g4 = *reinterpret_cast<const float4_t*>(g + j);
+        float4_t m4 = {0.f, 0.f, 0.f, 0.f};
+        if (m) m4 = *reinterpret_cast<const float4_t*>(m + j);
+        float4_t v4 = *reinterpret_cast<const float4_t*>(v + j);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          float w = w4[c], mm = m4[c], vv = v4[c];
+          op(w, g4[c], mm, vv);
+          w4[c] = w; m4[c] = mm; v4[c] = vv;
+        }
+        *reinterpret_cast<float4_t*>(p + j) = w4;
+        if (m) *reinterpret_cast<float4_t*>(m + j) = m4;
+        *reinterpret_cast<float4_t*>(v + j) = v4;
+      }
+      if (e) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e4[c] = e4[c] * ema_d + omd * w4[c];
+        *reinterpret_cast<float4_t*>(e + j) = e4;
+      }
+    }
+    done = base + 4 * nvec;
+  }
+  for (long long i = done + threadIdx.x; i < end; i += 256) {
+    float w = p[i];
+    if (!skip) {
+      float mm = m ? m[i] : 0.f, vv = v[i];
+      op(w, g[i], mm, vv);
+      p[i] = w;
+      if (m) m[i] = mm;
+      v[i] = vv;
+    }
+    if (e) e[i] = e[i] * ema_d + omd * w;
+  }
+}
+
+__global__ __launch_bounds__(256)
+void y5_mt_adam_kernel(const y5_mt_tensor* __restrict__ tab, float* const* __restrict__ second, const MtStats* __restrict__ stats,
+                       const MtStepRec* __restrict__ rec, const MtAdamHyper h) {
+  const y5_mt_tensor t = tab[blockIdx.y];
+  const long long base = (long long)blockIdx.x * CHV;
+  if (base >= t.n) return;
+  float coef = 1.0f;
+  bool skip = false;
+  if (h.use_stats) {
+    skip = stats->found_inf != 0.f;
+    coef = stats->clip_coef;
+  }
+  if (skip && !t.ema) return;
+  const int gi = t.group & 3;
+  const MtAdamOp op{coef, h.inv_scale, h.wd[gi], h.decay[gi], h.b2, h.one_minus_b1, h.one_minus_b2, h.eps, -rec->step_size[gi], rec->bc2_sqrt, h.adamw};
+  mt_update_chunk(t, second[blockIdx.y], base, skip, h.ema_d, op);
+}
+
+__global__ __launch_bounds__(256)
+void y5_mt_rmsprop_kernel(const y5_mt_tensor* __restrict__ tab, float* const* __restrict__ second, const MtStats* __restrict__ stats, const MtRmsHyper h) {
+  const y5_mt_tensor t = tab[blockIdx.y];
+  const long long base = (long long)blockIdx.x * CHV;
+  if (base >= t.n) return;
+  float coef = 1.0f;
+  bool skip = false;
+  if (h.use_stats) {
+    skip = stats->found_inf != 0.f;
+    coef = stats->clip_coef;
+  }
+  if (skip && !t.ema) return;
+  const int gi = t.group & 3;
+  const MtRmsOp op{coef, h.inv_scale, h.wd[gi], h.lr[gi], h.alpha, h.one_minus_alpha, h.eps, h.mu, t.mom != nullptr};
+  mt_update_chunk(t, second[blockIdx.y], base, skip, h.ema_d, op);
+}
+
 // dst = dst * d + (1 - d) * src  over a table whose entries use (param = src, ema = dst): ModelEMA over float BUFFERS
 __global__ __launch_bounds__(256)
 void y5_mt_lerp_kernel(const y5_mt_tensor* __restrict__ tab, float d) {
@@ -135,9 +290,9 @@ void y5_mt_lerp_kernel(const y5_mt_tensor* __restrict__ tab, float d) {
   for (long long i = base + threadIdx.x; i < end; i += 256) dst[i] = dst[i] * d + omd * src[i];
 }
 
-static int mt_grid(int ntensors, long long max_numel, dim3* grid) {
+static int mt_grid(int ntensors, long long max_numel, dim3* grid, int ch = CH) {
   if (ntensors < 1 || ntensors > 65535 || max_numel < 1) return y5_fail(Y5_ERR_BAD_ARG, "multi-tensor op: bad tensor count / size");
-  const long long chunks = (max_numel + CH - 1) / CH;
+  const long long chunks = (max_numel + ch - 1) / ch;
   if (chunks > 0x7fffffffLL) return y5_fail(Y5_ERR_UNSUPPORTED, "multi-tensor op: tensor too large");
   *grid = dim3((unsigned)chunks, (unsigned)ntensors);
   return Y5_OK;
@@ -176,6 +331,51 @@ extern "C" int y5_mt_sgd_step(const y5_mt_tensor* table_dev, int ntensors, long 
   hipLaunchKernelGGL(y5_mt_sgd_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), table_dev,
                      reinterpret_cast<const MtStats*>(stats_dev), h);
   return y5_check_launch("y5_mt_sgd_step");
+}
+
+extern "C" int y5_mt_adam_step(const y5_mt_tensor* table_dev, void* const* second_dev, int ntensors, long long max_numel, const double* lr4,
+                               const double* wd4, double beta1, double beta2, double eps, int adamw, float inv_scale, const float* stats_dev,
+                               float ema_decay, float* step_dev, float* rec_dev, void* stream_) {
+  if (!table_dev || !second_dev || !lr4 || !wd4 || !step_dev || !rec_dev) return y5_fail(Y5_ERR_BAD_ARG, "mt_adam_step: null pointer");
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) return y5_fail(Y5_ERR_BAD_ARG, "mt_adam_step: bad betas / eps");
+  dim3 grid;
+  if (int rc = mt_grid(ntensors, max_numel, &grid, CHV)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const MtStats* stats = reinterpret_cast<const MtStats*>(stats_dev);
+  MtStepArgs a{};
+  MtAdamHyper h{};
+  for (int i = 0; i < 4; ++i) {
+    a.lr[i] = lr4[i];
+    h.wd[i] = (float)wd4[i];
+    h.decay[i] = (float)(1.0 - lr4[i] * wd4[i]);
+  }
+  a.b1 = beta1; a.b2 = beta2; a.bias = 1; a.use_stats = stats != nullptr;
+  h.b2 = (float)beta2; h.one_minus_b1 = (float)(1.0 - beta1); h.one_minus_b2 = (float)(1.0 - beta2); h.eps = (float)eps;
+  h.inv_scale = inv_scale; h.ema_d = ema_decay; h.adamw = adamw != 0; h.use_stats = stats != nullptr;
+  hipLaunchKernelGGL(y5_mt_step_prep_kernel, dim3(1), dim3(1), 0, st, step_dev, reinterpret_cast<MtStepRec*>(rec_dev), stats, a);
+  hipLaunchKernelGGL(y5_mt_adam_kernel, grid, dim3(256), 0, st, table_dev, reinterpret_cast<float* const*>(second_dev), stats,
+                     reinterpret_cast<const MtStepRec*>(rec_dev), h);
+  return y5_check_launch("y5_mt_adam_step");
+}
+
+extern "C" int y5_mt_rmsprop_step(const y5_mt_tensor* table_dev, void* const* second_dev, int ntensors, long long max_numel, const double* lr4,
+                                  const double* wd4, double alpha, double eps, double momentum, float inv_scale, const float* stats_dev,
+                                  float ema_decay, float* step_dev, void* stream_) {
+  if (!table_dev || !second_dev || !lr4 || !wd4 || !step_dev) return y5_fail(Y5_ERR_BAD_ARG, "mt_rmsprop_step: null pointer");
+  if (!(alpha >= 0.0 && eps >= 0.0 && momentum >= 0.0)) return y5_fail(Y5_ERR_BAD_ARG, "mt_rmsprop_step: bad alpha / eps / momentum");
+  dim3 grid;
+  if (int rc = mt_grid(ntensors, max_numel, &grid, CHV)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const MtStats* stats = reinterpret_cast<const MtStats*>(stats_dev);
+  MtStepArgs a{};
+  MtRmsHyper h{};
+  for (int i = 0; i < 4; ++i) { h.lr[i] = (float)lr4[i]; h.wd[i] = (float)wd4[i]; }
+  a.bias = 0; a.use_stats = stats != nullptr;
+  h.alpha = (float)alpha; h.one_minus_alpha = (float)(1.0 - alpha); h.eps = (float)eps; h.mu = (float)momentum;
+  h.inv_scale = inv_scale; h.ema_d = ema_decay; h.use_stats = stats != nullptr;
+  hipLaunchKernelGGL(y5_mt_step_prep_kernel, dim3(1), dim3(1), 0, st, step_dev, static_cast<MtStepRec*>(nullptr), stats, a);
+  hipLaunchKernelGGL(y5_mt_rmsprop_kernel, grid, dim3(256), 0, st, table_dev, reinterpret_cast<float* const*>(second_dev), stats, h);
+  return y5_check_launch("y5_mt_rmsprop_step");
 }
 
 extern "C" int y5_mt_lerp(const y5_mt_tensor* table_dev, int ntensors, long long max_numel, float decay, void* stream_) {

@@ -12,6 +12,7 @@ parameters and buffers are broadcast from rank 0 at construction; BatchNorm stat
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 from contextlib import contextmanager
@@ -204,9 +205,11 @@ def torch_distributed_zero_first(local_rank: int):
         dist.barrier()
 
 
-def smart_optimizer(model, name="Adam", lr=0.001, momentum=0.9, decay=1e-5):
+def smart_optimizer(model, name="Adam", lr=0.001, momentum=0.9, decay=1e-5, fused=False):
     """utils/torch_utils.py:257-290 (same defaults; train.py:227 passes every argument): 3 parameter groups -- biases (no decay),
-    BatchNorm weights (no decay), other weights (decay).  name="SGD" returns the fused HipSGD."""
+    BatchNorm weights (no decay), other weights (decay).  name="SGD" returns the fused HipSGD.  fused=True: "Adam", "AdamW" and
+    "RMSProp" return HipAdam / HipAdamW / HipRMSprop (same groups and hyper-parameters, the multi-tensor kernels of csrc/optim.hip)
+    instead of the torch optimizers, which stay the default."""
     g = [], [], []
     bn = tuple(v for k, v in nn.__dict__.items() if "Norm" in k)
     for v in model.modules():
@@ -218,11 +221,11 @@ def smart_optimizer(model, name="Adam", lr=0.001, momentum=0.9, decay=1e-5):
             else:
                 g[0].append(p)
     if name == "Adam":
-        optimizer = torch.optim.Adam(g[2], lr=lr, betas=(momentum, 0.999))
+        optimizer = (HipAdam if fused else torch.optim.Adam)(g[2], lr=lr, betas=(momentum, 0.999))
     elif name == "AdamW":
-        optimizer = torch.optim.AdamW(g[2], lr=lr, betas=(momentum, 0.999), weight_decay=0.0)
+        optimizer = (HipAdamW if fused else torch.optim.AdamW)(g[2], lr=lr, betas=(momentum, 0.999), weight_decay=0.0)
     elif name == "RMSProp":
-        optimizer = torch.optim.RMSprop(g[2], lr=lr, momentum=momentum)
+        optimizer = (HipRMSprop if fused else torch.optim.RMSprop)(g[2], lr=lr, momentum=momentum)
     elif name == "SGD":
         # same groups / hyper-parameters / state_dict layout as torch.optim.SGD; the step is one fused multi-tensor launch
         optimizer = HipSGD(g[2], lr=lr, momentum=momentum, nesterov=True)
@@ -233,21 +236,29 @@ def smart_optimizer(model, name="Adam", lr=0.001, momentum=0.9, decay=1e-5):
     return optimizer
 
 
-class HipSGD(torch.optim.Optimizer):
-    """SGD(momentum, nesterov, weight_decay) with torch.optim.SGD's constructor, param_groups and state (`momentum_buffer`), whose
-    step is the fused multi-tensor kernel of csrc/optim.hip.  `step()` = plain optimizer step (gradients as they are);
-    `step_fused(inv_scale, max_norm, ema, model)` folds train.py:413-421 into three launches: GradScaler unscale + inf check,
-    clip_grad_norm_, the update (skipped on device when a gradient is non-finite) and ModelEMA.update.
+class _HipMultiTensor(torch.optim.Optimizer):
+    """What the fused optimizers share: the device-resident y5_mt_tensor table and its cache, the norm pass, the EMA hand-over and
+    `step_fused` / `step`.  A subclass names its state tensors (`_row_state`), checks its groups (`_check_groups`) and launches its
+    update kernel (`_update`).
+    `step()` = plain optimizer step (gradients as they are); `step_fused(inv_scale, max_norm, ema, model)` folds train.py:413-421
+    into a few launches: GradScaler unscale + inf check, clip_grad_norm_, the update (skipped on device when a gradient is
+    non-finite) and ModelEMA.update.
     `lib` selects the kernel library (default: libyolov5_hip.so; the tests pass the host-compiled emulator for CPU tensors)."""
 
-    def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, lib=None):
-        if dampening != 0.0:
-            raise ValueError("HipSGD: dampening is not supported (the reference never sets it)")
-        if nesterov and momentum <= 0:
-            raise ValueError("Nesterov momentum requires a momentum")
-        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=nesterov))
+    def __init__(self, params, defaults, lib=None):
+        super().__init__(params, defaults)
         self._lib = lib
         self._cache = None
+
+    def _row_state(self, p, g, st):
+        """(first state tensor or None -> y5_mt_tensor.mom, second state tensor or None) of parameter p, created on first use."""
+        raise NotImplementedError
+
+    def _check_groups(self):
+        pass
+
+    def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
+        raise NotImplementedError
 
     def _library(self):
         if self._lib is None:
@@ -265,36 +276,39 @@ class HipSGD(torch.optim.Optimizer):
 
         from . import _lib
 
+        name = type(self).__name__
         if len(self.param_groups) > 4:
-            raise ValueError("HipSGD: at most 4 parameter groups")
+            raise ValueError(f"{name}: at most 4 parameter groups")
         rows = []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
                 if p.grad is None:
                     continue
                 if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
-                    raise TypeError("HipSGD: contiguous fp32 parameters and gradients only")
-                st = self.state[p]
-                if g["momentum"] != 0 and "momentum_buffer" not in st:
-                    st["momentum_buffer"] = torch.zeros_like(p)
-                mom = st.get("momentum_buffer")
+                    raise TypeError(f"{name}: contiguous fp32 parameters and gradients only")
+                mom, second = self._row_state(p, g, self.state[p])
+                for s in (mom, second):
+                    if s is not None and (s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != p.numel() or s.device != p.device):
+                        raise TypeError(f"{name}: state tensors must be contiguous fp32 of the parameter's size, on its device")
                 e = ema_pairs.get(id(p)) if ema_pairs else None
                 rows.append((p.data_ptr(), p.grad.data_ptr(), mom.data_ptr() if mom is not None else 0, e.data_ptr() if e is not None else 0,
-                             p.numel(), gi))
+                             p.numel(), gi, second.data_ptr() if second is not None else 0))
         key = tuple(rows)
         if self._cache is None or self._cache[0] != key:
             if not rows:
-                self._cache = (key, None, 0, 0, None, None)
+                self._cache = (key, None, 0, 0, None, None, None)
                 return self._cache
             dev = self.param_groups[0]["params"][0].device
             arr = (_lib.MtTensor * len(rows))()
-            for r, (pp, gp, mp, ep, n, gi) in zip(arr, rows):
+            for r, (pp, gp, mp, ep, n, gi, _) in zip(arr, rows):
                 r.param, r.grad, r.mom, r.ema, r.n, r.group = pp, gp, mp or None, ep or None, n, gi
             tab = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy()).to(dev)
             max_n = max(r[4] for r in rows)
             ws = _lib.workspace(self._library().y5_mt_workspace_bytes(len(rows), max_n), dev)
             stats = torch.zeros(4, dtype=torch.float32, device=dev)
-            self._cache = (key, tab, len(rows), max_n, ws, stats)
+            # the second state tensor of every row: a device array of pointers parallel to the table (y5_mt_tensor keeps its layout)
+            second = torch.tensor([r[6] for r in rows], dtype=torch.int64).to(dev) if any(r[6] for r in rows) else None
+            self._cache = (key, tab, len(rows), max_n, ws, stats, second)
         return self._cache
 
     @staticmethod
@@ -311,7 +325,7 @@ class HipSGD(torch.optim.Optimizer):
         from . import _lib
 
         if self._lib is None and any(not _lib.accepts(p) for g in self.param_groups for p in g["params"]):
-            raise RuntimeError("HipSGD: parameters must live on the GPU (there is no CPU execution path)")
+            raise RuntimeError(f"{type(self).__name__}: parameters must live on the GPU (there is no CPU execution path)")
         lib = self._library()
         ema_pairs, d = None, 0.0
         if ema is not None:
@@ -320,23 +334,17 @@ class HipSGD(torch.optim.Optimizer):
             ema.updates += 1
             d = float(ema.decay(ema.updates))
             ema_pairs = ema.param_pairs(model)
-        key, tab, n, max_n, ws, stats = self._tables(ema_pairs)
+        key, tab, n, max_n, ws, stats, second = self._tables(ema_pairs)
         if n == 0:
             return None
         dev = tab.device
         st = self._stream(dev)
-        g0 = self.param_groups[0]
-        for g in self.param_groups:
-            if g["momentum"] != g0["momentum"] or g["nesterov"] != g0["nesterov"]:
-                raise ValueError("HipSGD: momentum / nesterov must be the same in every group")
-        lr4 = (C.c_float * 4)(*([float(g["lr"]) for g in self.param_groups] + [0.0] * (4 - len(self.param_groups))))
-        wd4 = (C.c_float * 4)(*([float(g["weight_decay"]) for g in self.param_groups] + [0.0] * (4 - len(self.param_groups))))
+        self._check_groups()
         use_stats = max_norm > 0 or inv_scale != 1.0
         if use_stats:
             _lib.check(lib.y5_mt_grad_norm(C.c_void_p(tab.data_ptr()), n, max_n, float(inv_scale), float(max_norm), C.c_void_p(stats.data_ptr()),
                                            C.c_void_p(ws.data_ptr()), ws.numel(), st), lib)
-        _lib.check(lib.y5_mt_sgd_step(C.c_void_p(tab.data_ptr()), n, max_n, lr4, wd4, float(g0["momentum"]), int(bool(g0["nesterov"])),
-                                      float(inv_scale), C.c_void_p(stats.data_ptr()) if use_stats else None, d, st), lib)
+        self._update(lib, tab, second, n, max_n, float(inv_scale), C.c_void_p(stats.data_ptr()) if use_stats else None, d, st)
         if ema is not None:
             ema.lerp_rest(model, d, lib, st, skip=set(k[0] for k in key))
         _state.bump_weights_epoch()  # parameters (and the EMA's) were written through raw pointers: cached eval plans re-pack
@@ -350,6 +358,201 @@ class HipSGD(torch.optim.Optimizer):
                 loss = closure()
         self.step_fused()
         return loss
+
+    def _group_vectors(self):
+        """lr and weight_decay of the (up to four) groups, padded to the kernels' four slots."""
+        pad = [0.0] * (4 - len(self.param_groups))
+        return [float(g["lr"]) for g in self.param_groups] + pad, [float(g["weight_decay"]) for g in self.param_groups] + pad
+
+
+class HipSGD(_HipMultiTensor):
+    """SGD(momentum, nesterov, weight_decay) with torch.optim.SGD's constructor, param_groups and state (`momentum_buffer`), whose
+    step is the fused multi-tensor kernel of csrc/optim.hip: `step_fused` is three launches (norm, finish, update)."""
+
+    def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, lib=None):
+        if dampening != 0.0:
+            raise ValueError("HipSGD: dampening is not supported (the reference never sets it)")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=nesterov), lib)
+
+    def _row_state(self, p, g, st):
+        if g["momentum"] != 0 and "momentum_buffer" not in st:
+            st["momentum_buffer"] = torch.zeros_like(p)
+        return st.get("momentum_buffer"), None
+
+    def _check_groups(self):
+        g0 = self.param_groups[0]
+        for g in self.param_groups:
+            if g["momentum"] != g0["momentum"] or g["nesterov"] != g0["nesterov"]:
+                raise ValueError("HipSGD: momentum / nesterov must be the same in every group")
+
+    def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
+        from . import _lib
+
+        lr, wd = self._group_vectors()
+        g0 = self.param_groups[0]
+        _lib.check(lib.y5_mt_sgd_step(C.c_void_p(tab.data_ptr()), n, max_n, (C.c_float * 4)(*lr), (C.c_float * 4)(*wd), float(g0["momentum"]),
+                                      int(bool(g0["nesterov"])), inv_scale, stats, d, st), lib)
+
+
+def _plain(v):
+    return tuple(float(x) for x in v) if isinstance(v, (list, tuple)) else v
+
+
+class _HipStepCounted(_HipMultiTensor):
+    """Adam / AdamW / RMSProp: torch's optimizers keep a `step` count per parameter.  Here it is ONE 0-dim fp32 device tensor that
+    every `state[p]["step"]` refers to (torch keeps `step` on the device too for capturable / fused); the kernels advance it, and only
+    when the step is taken, so a GradScaler skip costs no host read.  `state_dict()` writes it out as torch's own layout (one host
+    tensor per parameter) and `load_state_dict` adopts a torch.optim state dict: the `step` values must agree."""
+
+    _UNSUPPORTED = ()
+    _SHARED = ()
+
+    def __init__(self, params, defaults, lib=None, **flags):
+        for k in self._UNSUPPORTED:
+            if flags.get(k):
+                raise ValueError(f"{type(self).__name__}: {k} is not supported")
+        self._step = None
+        self._rec = None
+        super().__init__(params, defaults, lib)
+        self._check_groups()
+
+    def _check_groups(self):
+        name = type(self).__name__
+        g0 = self.param_groups[0]
+        for g in self.param_groups:
+            for k in self._UNSUPPORTED:
+                if g.get(k):
+                    raise ValueError(f"{name}: {k} is not supported")
+            for k in self._SHARED:
+                if _plain(g[k]) != _plain(g0[k]):
+                    raise ValueError(f"{name}: {k} must be the same in every group")
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self._check_groups()
+
+    def _step_tensor(self, dev):
+        if self._step is None or self._step.device != dev:
+            old = self._step
+            self._step = torch.zeros((), dtype=torch.float32, device=dev)
+            self._rec = torch.zeros(8, dtype=torch.float32, device=dev)
+            if old is not None:
+                self._step.copy_(old)
+        return self._step
+
+    def _states(self, p, st, names):
+        if "step" not in st:
+            st["step"] = self._step_tensor(p.device)
+        elif st.get("step") is not self._step:
+            raise RuntimeError(f"{type(self).__name__}: state[p]['step'] was replaced; use load_state_dict to restore a state")
+        for k in names:
+            if k not in st:
+                st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return [st[k] for k in names]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self._step is not None:
+            t = float(self._step)
+            # (Optimizer.state_dict hands out the live per-parameter dicts: replace `step` in copies of them)
+            sd["state"] = {k: dict(st, step=torch.tensor(t, dtype=torch.float32)) if "step" in st else st for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        steps = {float(st["step"]) for st in state_dict["state"].values() if "step" in st}
+        if len(steps) > 1:
+            raise ValueError(f"{type(self).__name__}: the parameters' `step` values differ ({sorted(steps)}): one count per optimizer here")
+        super().load_state_dict(state_dict)
+        self._check_groups()
+        t = self._step_tensor(self.param_groups[0]["params"][0].device)
+        t.fill_(steps.pop() if steps else 0.0)
+        for st in self.state.values():
+            if st:
+                st["step"] = t
+        self._cache = None
+
+
+class HipAdam(_HipStepCounted):
+    """torch.optim.Adam's constructor, param_groups and state (`step`, `exp_avg`, `exp_avg_sq`) on y5_mt_adam_step (csrc/optim.hip):
+    `step_fused` is four launches (norm, finish, step count + bias corrections, update)."""
+
+    _UNSUPPORTED = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused")
+    _SHARED = ("betas", "eps")
+    _ADAMW = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=False, differentiable=False, lib=None):
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"{type(self).__name__}: invalid lr / betas / eps / weight_decay")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                        differentiable=False, fused=None, decoupled_weight_decay=self._ADAMW)
+        super().__init__(params, defaults, lib, amsgrad=amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable)
+
+    def _check_groups(self):
+        super()._check_groups()
+        for g in self.param_groups:
+            if bool(g.get("decoupled_weight_decay", self._ADAMW)) != self._ADAMW:
+                raise ValueError(f"{type(self).__name__}: decoupled_weight_decay={g['decoupled_weight_decay']} belongs to the other class")
+
+    def _row_state(self, p, g, st):
+        return self._states(p, st, ("exp_avg", "exp_avg_sq"))
+
+    def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
+        from . import _lib
+
+        lr, wd = self._group_vectors()
+        g0 = self.param_groups[0]
+        step = self._step_tensor(tab.device)
+        _lib.check(lib.y5_mt_adam_step(C.c_void_p(tab.data_ptr()), C.c_void_p(second.data_ptr()), n, max_n, (C.c_double * 4)(*lr), (C.c_double * 4)(*wd),
+                                       float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), int(self._ADAMW), inv_scale, stats, d,
+                                       C.c_void_p(step.data_ptr()), C.c_void_p(self._rec.data_ptr()), st), lib)
+
+
+class HipAdamW(HipAdam):
+    """torch.optim.AdamW (decoupled weight decay: p *= 1 - lr * weight_decay before the Adam update)."""
+
+    _ADAMW = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, lib=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, lib=lib)
+
+
+class HipRMSprop(_HipStepCounted):
+    """torch.optim.RMSprop(centered=False)'s constructor, param_groups and state (`step`, `square_avg`, `momentum_buffer` when
+    momentum > 0) on y5_mt_rmsprop_step (csrc/optim.hip)."""
+
+    _UNSUPPORTED = ("centered", "maximize", "foreach", "capturable", "differentiable")
+    _SHARED = ("alpha", "eps", "momentum")
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False, capturable=False, foreach=None,
+                 maximize=False, differentiable=False, lib=None):
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not 0.0 <= momentum or not 0.0 <= alpha:
+            raise ValueError("HipRMSprop: invalid lr / alpha / eps / weight_decay / momentum")
+        defaults = dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=False, weight_decay=weight_decay, capturable=False, foreach=None,
+                        maximize=False, differentiable=False)
+        super().__init__(params, defaults, lib, centered=centered, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable)
+
+    def _row_state(self, p, g, st):
+        if g["momentum"] > 0:
+            buf, sq = self._states(p, st, ("momentum_buffer", "square_avg"))
+            return buf, sq
+        return None, self._states(p, st, ("square_avg",))[0]
+
+    def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
+        from . import _lib
+
+        lr, wd = self._group_vectors()
+        g0 = self.param_groups[0]
+        step = self._step_tensor(tab.device)
+        _lib.check(lib.y5_mt_rmsprop_step(C.c_void_p(tab.data_ptr()), C.c_void_p(second.data_ptr()), n, max_n, (C.c_double * 4)(*lr),
+                                          (C.c_double * 4)(*wd), float(g0["alpha"]), float(g0["eps"]), float(g0["momentum"]), inv_scale, stats, d,
+                                          C.c_void_p(step.data_ptr()), st), lib)
 
 
 class ModelEMA:

@@ -9,7 +9,8 @@ way train.py trains it:
   every `accumulate` batches: unscale + clip_grad_norm_(10) + optimizer step + scaler update + zero_grad + EMA update;
   per epoch: scheduler.step().
 
-MI355X mapping: forward / backward are the TrainEngine plans, the optimizer block is three fused launches (HipSGD.step_fused), the
+MI355X mapping: forward / backward are the TrainEngine plans, the optimizer block is three fused launches (HipSGD.step_fused; HipAdam / HipAdamW /
+HipRMSprop with fused_optimizer=True: four), the
 GradScaler's found-inf flag stays on the device -- the update it guards is skipped there (csrc/optim.hip) and the host reads the
 flag with a non-blocking copy one iteration later to adjust the scale (no pipeline drain per step).
 """
@@ -91,7 +92,7 @@ def host_amp_step(optimizer, parameters, scaler, max_norm=10.0):
     """GradScaler.unscale_ + clip_grad_norm_ + GradScaler.step for ANY torch optimizer (the Adam / AdamW / RMSProp choices of
     smart_optimizer; train.py:411-414): unscale in place, clip, and SKIP optimizer.step() when the unscaled gradients are not finite;
     the flag goes to the scale policy (back-off / growth at the next update()).  Returns True when the step was taken.
-    One host sync (the norm) -- this is the non-fused path; HipSGD.step_fused keeps the flag on the device."""
+    One host sync (the norm) -- this is the non-fused path; the Hip* optimizers' step_fused keeps the flag on the device."""
     params = [p for p in parameters if p.grad is not None]
     if scaler.scale != 1.0 and params:
         torch._foreach_mul_([p.grad for p in params], 1.0 / scaler.scale)
@@ -105,7 +106,7 @@ def host_amp_step(optimizer, parameters, scaler, max_norm=10.0):
 
 def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_lr=False, amp=True, ema=True, world_size=1, rank=-1,
           optimizer_name="SGD", max_norm=10.0, start_epoch=0, on_batch_end=None, nbs=64, val_loader=None, noval=False, sync_bn=False,
-          overlap=True, autoanchor=None, imgsz=None):
+          overlap=True, autoanchor=None, imgsz=None, fused_optimizer=False):
     """Runs `epochs` epochs over `loader` (iterable of (imgs uint8|float BCHW, targets (nt, 6), *rest), re-iterable, len() = batches
     per epoch).  Returns dict(model, ema, optimizer, scheduler, scaler, mloss per epoch, losses per iteration, lr per epoch).
     rank / world_size as train.py's RANK / WORLD_SIZE (-1 / 1: single process; otherwise torch.distributed is initialised and the
@@ -117,7 +118,9 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
     (train.py:314-315 `check_anchors(dataset, model, thr=hyp['anchor_t'], imgsz)`: rank -1 / 0 of a run with start_epoch == 0, then a broadcast
     from rank 0); imgsz defaults to the loader's `s`, else 640.  NOTE the default differs from train.py's: there AutoAnchor runs unless
     `--noautoanchor` is given, here it runs only when asked for -- with None nothing changes and no RNG is consumed.  The result
-    (bpr, aat, replaced) is returned under "autoanchor"."""
+    (bpr, aat, replaced) is returned under "autoanchor".
+    fused_optimizer: smart_optimizer(fused=True) -- "Adam" / "AdamW" / "RMSProp" take the device path of "SGD" (step_fused) instead of host_amp_step.
+    Off by default, as the reference's optimizers are."""
     from .yolo import Segment
 
     seg = isinstance(de_parallel(model).model[-1], Segment)
@@ -140,7 +143,7 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
             aa_result = check_anchors(autoanchor, model, thr=hyp["anchor_t"], imgsz=imgsz or getattr(autoanchor, "s", None) or 640)
         if rank != -1 and world_size > 1:
             dist.broadcast(det.anchors, 0)
-    optimizer = smart_optimizer(model, optimizer_name, hyp["lr0"], hyp["momentum"], hyp["weight_decay"])  # :237
+    optimizer = smart_optimizer(model, optimizer_name, hyp["lr0"], hyp["momentum"], hyp["weight_decay"], fused=fused_optimizer)  # :237
     lf = lr_lambda(epochs, hyp["lrf"], cos_lr)
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda=lf)          # :248
     ema_obj = ModelEMA(model) if (ema and rank in (-1, 0)) else None                # :251
