@@ -359,6 +359,20 @@ def workspace(nbytes, device):
     return t[off:off + int(nbytes)]
 
 
+def device_table(arr, device):
+    """Device byte tensor holding a copy of a ctypes array: the job and tensor tables the batched launches read."""
+    import torch
+
+    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
+
+
+def dtype_code(dtype):
+    """Y5_* code of a torch dtype (KeyError for one the image kernels do not write)."""
+    import torch
+
+    return {torch.uint8: Y5_U8, torch.float16: Y5_F16, torch.float32: Y5_F32}[dtype]
+
+
 def lib():
     """The loaded kernel library.  Raises RuntimeError (never falls back) if it is not built / not loadable."""
     global _lib

@@ -64,11 +64,10 @@ def _launch(ims, geos, H, W, pad, swap_rb, out, chw, div255):
         j.src, j.h0, j.w0, j.stride = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
         j.nw, j.nh, j.top, j.left = g["new_unpad"][0], g["new_unpad"][1], g["top"], g["left"]
     dev = out.device
-    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev, non_blocking=False)
-    code = {torch.uint8: _lib.Y5_U8, torch.float16: _lib.Y5_F16, torch.float32: _lib.Y5_F32}[out.dtype]
+    table = _lib.device_table(jobs, dev)
     lib = _lib.lib()
-    rc = lib.y5_letterbox_batch(C.c_void_p(table.data_ptr()), len(ims), H, W, pad, int(swap_rb), C.c_void_p(out.data_ptr()), code, int(chw),
-                                int(div255), _lib.stream(dev))
+    rc = lib.y5_letterbox_batch(C.c_void_p(table.data_ptr()), len(ims), H, W, pad, int(swap_rb), C.c_void_p(out.data_ptr()), _lib.dtype_code(out.dtype),
+                                int(chw), int(div255), _lib.stream(dev))
     _lib.check(rc, lib)
     return out  # `table` may be released here: the caching allocator re-uses it in stream order, after the launch
 
@@ -145,11 +144,11 @@ def classify_transform_batch(ims, size=224, half=False, mean=IMAGENET_MEAN, std=
     jobs = (_lib.ClassifyJob * len(ims))()
     for j, im in zip(jobs, ims):
         j.src, j.h0, j.w0, j.stride = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
-    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev, non_blocking=False)
+    table = _lib.device_table(jobs, dev)
     out = torch.empty((len(ims), 3, size, size), dtype=torch.float16 if half else torch.float32, device=dev)
     lib = _lib.lib()
     rc = lib.y5_classify_transform_batch(C.c_void_p(table.data_ptr()), len(ims), size, C.c_void_p(_classify_lut(dev, mean, std).data_ptr()),
-                                         C.c_void_p(out.data_ptr()), _lib.Y5_F16 if half else _lib.Y5_F32, _lib.stream(dev))
+                                         C.c_void_p(out.data_ptr()), _lib.dtype_code(out.dtype), _lib.stream(dev))
     _lib.check(rc, lib)
     return out
 

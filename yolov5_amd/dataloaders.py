@@ -1,20 +1,34 @@
-"""Training input pipeline (utils/dataloaders.py:696-863 `LoadImagesAndLabels.__getitem__` with augment = True, rect = False -- the mosaic
-branch and, where the hyp['mosaic'] gate sends a sample there, the letterbox branch :710-733 -- + `collate_fn`;
-utils/augmentations.py:69-83 `augment_hsv`, :118-209 `random_perspective`, :246-258 `box_candidates`) with the pixel work on the
-device: the dataset's uint8 BGR images live in HBM, `MosaicLoader` draws the random numbers and does the geometry + label transform
-of a whole batch on the host (a few hundred floats) and ONE `y5_mosaic_batch` launch renders the (B, 3, s, s) batch -- resized
-tiles, canvas, warp, HSV, flips, layout -- directly in the a0 tensor contract of the model (uint8, or fp16 / 255).  At the training
-rates of this engine (3 k img/s per GPU) the reference's 8 cv2 worker processes cannot keep a GPU fed.
+"""Input pipelines with the pixel work on the device: the dataset's uint8 BGR images live in HBM, the host draws the random numbers and does
+the geometry + label transform of a whole batch (a few hundred floats) in the reference's own expressions, and ONE launch renders the batch
+directly in the a0 tensor contract of the model (uint8, or fp16 / 255).  At the training rates of this engine (3 k img/s per GPU) the
+reference's 8 cv2 worker processes cannot keep a GPU fed.
 
-Random draws follow the reference's ORDER per sample (documented in `draw_sample`), so that a `random.seed()` / `np.random.seed()`-ed
-run consumes the generators exactly as `__getitem__` does; they can also be passed in (parity tests).
-Segmentation datasets (utils/segment/dataloaders.py:130-301 `LoadImagesAndLabelsAndMasks`, utils/segment/augmentations.py:14-91): the
-second half of this file -- `draw_sample_seg`, `seg_mosaic_batch`, `SegMosaicLoader`, `seg_letterbox_batch`, `SegValLoader`.  The image half
-is the SAME `y5_mosaic_batch` launch; the polygons go through the reference's own float64 expressions on the host and ONE `y5_polygon_masks`
-call (csrc/seg_data.h) rasterises, shrinks, orders and flips the masks of the batch.
-Detection validation (`LoadImagesAndLabels(augment=False, rect=..., pad=...)`, :589-612 rect ordering and batch shapes, :710-736 the letterbox
-branch, :784-788 `load_image` with INTER_AREA for a down-scale, + `collate_fn`): the third part of this file -- `area_jobs`,
-`letterbox_area_batch` (ONE `y5_letterbox_area_batch` launch per batch, csrc/val_data.h) and `ValLoader`.
+The loaders and what they restate:
+    MosaicLoader / mosaic_batch            utils/dataloaders.py:696-863 `LoadImagesAndLabels.__getitem__` (augment = True, rect = False: the mosaic
+                                           branch and, where the hyp['mosaic'] gate sends a sample there, the letterbox branch :710-733) + `collate_fn`;
+                                           utils/augmentations.py:69-83 `augment_hsv`, :118-209 `random_perspective`, :246-258 `box_candidates`
+    SegMosaicLoader / seg_mosaic_batch     utils/segment/dataloaders.py:130-301 `LoadImagesAndLabelsAndMasks`, utils/segment/augmentations.py:14-91;
+                                           the polygons go through the reference's float64 expressions on the host and ONE `y5_polygon_masks` call
+                                           (csrc/seg_data.h) rasterises, shrinks, orders and flips the masks of the batch
+    SegValLoader / seg_letterbox_batch     the augment = False, rect = False branch of the same `__getitem__`
+    ValLoader / letterbox_area_batch       `LoadImagesAndLabels(augment=False, rect=..., pad=...)`: :589-612 rect ordering and batch shapes, :710-736 the
+                                           letterbox branch, :784-788 `load_image` with INTER_AREA for a down-scale, + `collate_fn`; ONE
+                                           `y5_letterbox_area_batch` launch per batch (csrc/val_data.h)
+    ClassificationLoader                   utils/dataloaders.py:949-1013, the torch_transforms branch (augmentations.classify_transform_batch)
+
+The host rules they share, each written once:
+    draws        `_perspective_draws`, `_mosaic_draws`, `_draw_sample`: the reference's ORDER per sample, so that a `random.seed()` /
+                 `np.random.seed()`-ed run consumes the generators exactly as `__getitem__` does (the generators can also be passed in: parity
+                 tests).  `draw_sample` and `draw_sample_seg` differ in the shuffle of the tile indices and in how the mixup partner is picked.
+    geometry     `_resized_hw` (load_image; every loader), `_tile_rects`, `_affine`, `_invert_affine`, `_fill_job` (one y5_mosaic_batch job:
+                 both training loaders and `seg_letterbox_batch`), `_check_image` (the image contract, also `area_jobs`)
+    labels       `_xywhn2xyxy` (`_canvas_boxes`, `ValLoader`), `_canvas_boxes` (`_labels`, `_seg_labels`, `seg_letterbox_batch`), `_xyn2xy`
+                 (`_seg_labels`, `seg_letterbox_batch`), `_box_candidates` (`_labels`, `_seg_labels`), `_finish_labels` (every detection and
+                 segmentation loader)
+    batches      `_assemble` (the job and label loop of `mosaic_batch` and `seg_mosaic_geometry`: mixup partners, HSV tables, batch index),
+                 `_render` (the y5_mosaic_batch launch: both training loaders, `seg_letterbox_batch`), `_masks_and_targets` (both segmentation
+                 batch functions), `_targets`
+    epochs       `MosaicLoader._epoch_order` (seeded shuffle, rank stride, padding); `SegMosaicLoader` overrides only `_batch`
 Not covered: reading images and label files from disk and the caches, image_weights, rect batches for TRAINING, collate_fn4, copy_paste,
 albumentations, perspective != 0."""
 from __future__ import annotations
@@ -33,43 +47,62 @@ HYP_AUG = {"hsv_h": 0.015, "hsv_s": 0.7, "hsv_v": 0.4, "degrees": 0.0, "translat
            "flipud": 0.0, "fliplr": 0.5, "mosaic": 1.0, "mixup": 0.0, "copy_paste": 0.0}  # data/hyps/hyp.scratch-low.yaml:25-37
 
 
-def draw_sample(index, n_images, s, hyp, rng=random, np_rng=np.random):
-    """Random numbers of one sample in the reference's order: mosaic gate (dataloaders.py:701); centre yc, xc (:802); three extra
-    indices + shuffle (:803-804); perspective x2, angle, scale, shear x2, translate x2 (augmentations.py:135-156); mixup gate
-    (dataloaders.py:707); three HSV gains from numpy (augmentations.py:72); flipud, fliplr gates (dataloaders.py:747,753)."""
-    d = {"mosaic": rng.random() < hyp["mosaic"]}
-    if d["mosaic"]:
-        d["yc"], d["xc"] = (int(rng.uniform(-x, 2 * s + x)) for x in (-s // 2, -s // 2))
-        idx = [index, *rng.choices(range(n_images), k=3)]
-        rng.shuffle(idx)
-        d["indices"] = idx
-    else:   # letterbox branch (dataloaders.py:710-733): the next draws are random_perspective's; no mixup gate on this side
-        d["indices"] = [index]
+def _perspective_draws(d, hyp, rng):
+    """random_perspective's eight (augmentations.py:135-156; segment/augmentations.py:42-61): perspective x2, angle, scale, shear x2, translate x2."""
     d["persp"] = (rng.uniform(-hyp["perspective"], hyp["perspective"]), rng.uniform(-hyp["perspective"], hyp["perspective"]))
     d["angle"] = rng.uniform(-hyp["degrees"], hyp["degrees"])
     d["scale"] = rng.uniform(1 - hyp["scale"], 1 + hyp["scale"])
     d["shear"] = (rng.uniform(-hyp["shear"], hyp["shear"]), rng.uniform(-hyp["shear"], hyp["shear"]))
     d["translate"] = (rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]), rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]))
-    if d["mosaic"] and rng.random() < hyp["mixup"]:
-        # dataloaders.py:707-708: random.choice(indices), the partner mosaic's own draws (load_mosaic -> random_perspective), np.random.beta in mixup()
-        m = {"mosaic": True}
-        i2 = rng.choice(range(n_images))
-        m["yc"], m["xc"] = (int(rng.uniform(-x, 2 * s + x)) for x in (-s // 2, -s // 2))
-        idx = [i2, *rng.choices(range(n_images), k=3)]
-        rng.shuffle(idx)
-        m["indices"] = idx
-        m["persp"] = (rng.uniform(-hyp["perspective"], hyp["perspective"]), rng.uniform(-hyp["perspective"], hyp["perspective"]))
-        m["angle"] = rng.uniform(-hyp["degrees"], hyp["degrees"])
-        m["scale"] = rng.uniform(1 - hyp["scale"], 1 + hyp["scale"])
-        m["shear"] = (rng.uniform(-hyp["shear"], hyp["shear"]), rng.uniform(-hyp["shear"], hyp["shear"]))
-        m["translate"] = (rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]), rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]))
-        d["partner"], d["mix_r"] = m, float(np_rng.beta(32.0, 32.0))
+    return d
+
+
+def _mosaic_draws(index, n_images, s, hyp, rng, shuffle):
+    """Draws of one mosaic (load_mosaic -> random_perspective): centre yc, xc; three extra indices, shuffled with `index` when `shuffle`; the eight."""
+    d = {"mosaic": True}
+    d["yc"], d["xc"] = (int(rng.uniform(-x, 2 * s + x)) for x in (-s // 2, -s // 2))
+    d["indices"] = [index, *rng.choices(range(n_images), k=3)]
+    if shuffle:
+        rng.shuffle(d["indices"])
+    return _perspective_draws(d, hyp, rng)
+
+
+def _draw_sample(index, n_images, s, hyp, rng, np_rng, shuffle, partner):
+    """The draw order both `__getitem__`s share: mosaic gate; the mosaic's draws; mixup gate, `partner()` index, the partner mosaic's own draws,
+    np.random.beta in mixup(); three HSV gains from numpy (augmentations.py:72); flipud, fliplr gates."""
+    if rng.random() < hyp["mosaic"]:
+        d = _mosaic_draws(index, n_images, s, hyp, rng, shuffle)
+        if rng.random() < hyp["mixup"]:
+            d["partner"] = _mosaic_draws(partner(), n_images, s, hyp, rng, shuffle)
+            d["mix_r"] = float(np_rng.beta(32.0, 32.0))
+    else:   # letterbox branch (dataloaders.py:710-733): the next draws are random_perspective's; no mixup gate on this side
+        d = _perspective_draws({"mosaic": False, "indices": [index]}, hyp, rng)
     d["hsv"] = np_rng.uniform(-1, 1, 3) * [hyp["hsv_h"], hyp["hsv_s"], hyp["hsv_v"]] + 1
     d["flipud"] = rng.random() < hyp["flipud"]
     d["fliplr"] = rng.random() < hyp["fliplr"]
+    return d
+
+
+def draw_sample(index, n_images, s, hyp, rng=random, np_rng=np.random):
+    """Random numbers of one sample in the reference's order: mosaic gate (dataloaders.py:701); centre yc, xc (:802); three extra
+    indices + shuffle (:803-804); perspective x2, angle, scale, shear x2, translate x2 (augmentations.py:135-156); mixup gate
+    (dataloaders.py:707), partner = random.choice(indices) (:708); three HSV gains from numpy (augmentations.py:72); flipud, fliplr gates
+    (dataloaders.py:747,753)."""
     if hyp["perspective"]:
         raise NotImplementedError("MosaicLoader: perspective != 0 (cv2.warpPerspective) is not implemented")
-    return d
+    return _draw_sample(index, n_images, s, hyp, rng, np_rng, True, lambda: rng.choice(range(n_images)))
+
+
+def draw_sample_seg(index, n_images, s, hyp, rng=random, np_rng=np.random):
+    """Random numbers of one sample in the order of the SEGMENTATION `__getitem__` (utils/segment/dataloaders.py), which is not `draw_sample`'s:
+    mosaic gate (:135); centre yc, xc (:239); three extra indices, NOT shuffled (:242); copy_paste draws nothing at p = 0 (:280);
+    random_perspective's eight (segment/augmentations.py:42-61); mixup gate (:141), partner = randint(0, n - 1) (:142), the partner mosaic's own
+    draws, np.random.beta (segment/augmentations.py:19); three HSV gains from numpy; flipud, fliplr gates (:212,219)."""
+    if hyp.get("copy_paste", 0.0):
+        raise NotImplementedError("SegMosaicLoader: copy_paste != 0 is not implemented")
+    if hyp["perspective"]:
+        raise NotImplementedError("SegMosaicLoader: perspective != 0 (cv2.warpPerspective) is not implemented")
+    return _draw_sample(index, n_images, s, hyp, rng, np_rng, False, lambda: rng.randint(0, n_images - 1))
 
 
 def _resized_hw(h0, w0, s):
@@ -125,24 +158,49 @@ def _invert_affine(M):
     return m
 
 
-def _labels(labels, d, hw, rects, M, width, height, s, pads=None):
-    """Label half of the sample up to random_perspective: tiles -> canvas pixels (xywhn2xyxy, :838 / :720), mosaic only: clip to the canvas
-    (:845-846), corners through M + hull + clip + box_candidates (augmentations.py:193-209,246-258) -> (k, 5) [cls, x1, y1, x2, y2] in output pixels.
-    pads: the (padw, padh) of each tile when they are not the integer tile offsets (letterbox branch: the FLOAT half-borders dw, dh)."""
+def _xywhn2xyxy(x, w, h, padw, padh):
+    """ultralytics.utils.ops.xywhn2xyxy (call sites utils/dataloaders.py:721,838), the reference's expressions: the TYPES of w, h, padw, padh decide
+    whether numpy evaluates them in float32 or float64, so the caller passes scalars made the way the reference makes them."""
+    y = x.copy()
+    y[..., 0] = w * (x[..., 0] - x[..., 2] / 2) + padw
+    y[..., 1] = h * (x[..., 1] - x[..., 3] / 2) + padh
+    y[..., 2] = w * (x[..., 0] + x[..., 2] / 2) + padw
+    y[..., 3] = h * (x[..., 1] + x[..., 3] / 2) + padh
+    return y
+
+
+def _canvas_boxes(labels, d, hw, pads, s):
+    """Tile labels -> canvas pixels (xywhn2xyxy, :838 / :720), mosaic only: clipped to the canvas (:845-846).
+    -> ((n, 5) float32 [cls, x1, y1, x2, y2], the number of rows of every tile)."""
     parts = []
-    for k, (i, (h, w), (x1a, y1a, _x2a, _y2a, x1b, y1b)) in enumerate(zip(d["indices"], hw, rects)):
+    for i, (h, w), (padw, padh) in zip(d["indices"], hw, pads):
         lb = np.array(labels[i], dtype=np.float32).reshape(-1, 5).copy()
         if lb.size:
-            xy, half = lb[:, 1:3].copy(), lb[:, 3:5] / 2
-            padw, padh = (x1a - x1b, y1a - y1b) if pads is None else pads[k]
-            lb[:, 1] = w * (xy[:, 0] - half[:, 0]) + padw
-            lb[:, 2] = h * (xy[:, 1] - half[:, 1]) + padh
-            lb[:, 3] = w * (xy[:, 0] + half[:, 0]) + padw
-            lb[:, 4] = h * (xy[:, 1] + half[:, 1]) + padh
+            lb[:, 1:] = _xywhn2xyxy(lb[:, 1:], w, h, padw, padh)
         parts.append(lb)
     t = np.concatenate(parts, 0)
     if d.get("mosaic", True):
         np.clip(t[:, 1:], 0, 2 * s, out=t[:, 1:])
+    return t, [len(lb) for lb in parts]
+
+
+def _box_candidates(t, new, scale, area_thr):
+    """box_candidates(box1=t[:, 1:5].T * scale, box2=new.T, area_thr) (augmentations.py:246-258; wh_thr = 2, ar_thr = 100, eps = 1e-16) and what
+    both random_perspectives do with it: -> (the rows of t it keeps, with their boxes replaced by `new`; the keep mask)."""
+    b1 = t[:, 1:5].T * scale
+    w1, h1 = b1[2] - b1[0], b1[3] - b1[1]
+    w2, h2 = new[:, 2] - new[:, 0], new[:, 3] - new[:, 1]
+    ar = np.maximum(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16))
+    keep = (w2 > 2) & (h2 > 2) & (w2 * h2 / (w1 * h1 + 1e-16) > area_thr) & (ar < 100)
+    t = t[keep]
+    t[:, 1:5] = new[keep]
+    return t, keep
+
+
+def _labels(labels, d, hw, pads, M, width, height, s):
+    """Label half of the sample up to random_perspective: `_canvas_boxes`, corners through M + hull + clip + box_candidates(area_thr = 0.10)
+    (augmentations.py:193-209) -> (k, 5) [cls, x1, y1, x2, y2] in output pixels."""
+    t, _ = _canvas_boxes(labels, d, hw, pads, s)
     n = len(t)
     if n:
         pts = np.ones((n * 4, 3))
@@ -152,13 +210,7 @@ def _labels(labels, d, hw, rects, M, width, height, s, pads=None):
         new = np.concatenate((xs.min(1), ys.min(1), xs.max(1), ys.max(1))).reshape(4, n).T
         new[:, [0, 2]] = new[:, [0, 2]].clip(0, width)
         new[:, [1, 3]] = new[:, [1, 3]].clip(0, height)
-        b1 = t[:, 1:5].T * d["scale"]
-        w1, h1 = b1[2] - b1[0], b1[3] - b1[1]
-        w2, h2 = new[:, 2] - new[:, 0], new[:, 3] - new[:, 1]
-        ar = np.maximum(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16))
-        keep = (w2 > 2) & (h2 > 2) & (w2 * h2 / (w1 * h1 + 1e-16) > 0.10) & (ar < 100)
-        t = t[keep]
-        t[:, 1:5] = new[keep]
+        t, _ = _box_candidates(t, new, d["scale"], 0.10)
     return t
 
 
@@ -184,20 +236,28 @@ def _finish_labels(t, d, width, height):
     return res
 
 
+def _check_image(im, who):
+    """The image contract of the batched kernels: uint8 (h, w, 3) with contiguous rows -> (h0, w0)."""
+    if not (_lib.accepts(im) and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
+        raise ValueError(f"{who}: images must be uint8 (h, w, 3) device tensors with contiguous rows")
+    return int(im.shape[0]), int(im.shape[1])
+
+
 def _fill_job(j, images, d, s):
-    """Geometry half of one job of the y5_mosaic_batch table (tiles, rectangles, inverse affine map) -> (hw, rects, pads, M, width, height)."""
+    """Geometry half of one job of the y5_mosaic_batch table (tiles, rectangles, inverse affine map) -> (hw, pads, M, width, height): the resized
+    (h, w) of every tile and the (padw, padh) that move its labels to the canvas -- the integer tile offsets of a mosaic, the FLOAT half-borders
+    dw, dh on the letterbox branch."""
     hw = []
     for t, i in enumerate(d["indices"]):
         im = images[i]
-        if not (_lib.accepts(im) and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
-            raise ValueError("mosaic_batch: images must be uint8 (h, w, 3) device tensors with contiguous rows")
-        h0, w0 = int(im.shape[0]), int(im.shape[1])
+        h0, w0 = _check_image(im, "mosaic_batch")
         rh, rw = _resized_hw(h0, w0, s)
         hw.append((rh, rw))
         j.src[t], j.h0[t], j.w0[t], j.stride[t], j.rh[t], j.rw[t] = im.data_ptr(), h0, w0, int(im.stride(0)), rh, rw
-    mosaic, pads = d.get("mosaic", True), None
+    mosaic = d.get("mosaic", True)
     if mosaic:
         rects = _tile_rects(hw, d["yc"], d["xc"], s)
+        pads = [(x1a - x1b, y1a - y1b) for x1a, y1a, _x2a, _y2a, x1b, y1b in rects]
     else:
         # letterbox(auto=False, scaleup=True) of an image whose longest side already is s (augmentations.py:85-115): r = 1, no second resize;
         # the image sits at (left, top) = (round(dw - 0.1), round(dh - 0.1)) of an s x s canvas of 114s, the labels move by the FLOAT dw, dh
@@ -212,7 +272,7 @@ def _fill_job(j, images, d, s):
     A = _invert_affine(M)
     for k in range(6):
         j.A[k] = float(A.reshape(-1)[k])
-    return hw, rects, pads, M, width, height
+    return hw, pads, M, width, height
 
 
 def _finish_job(j, d, use_hsv):
@@ -227,13 +287,49 @@ def _finish_job(j, d, use_hsv):
 
 def _render(jobs, B, s, dev, dtype, normalize):
     """The y5_mosaic_batch launch over a filled job table -> (B, 3, s, s)."""
-    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev)
+    table = _lib.device_table(jobs, dev)
     out = torch.empty((B, 3, s, s), dtype=dtype, device=dev)
-    code = {torch.uint8: _lib.Y5_U8, torch.float16: _lib.Y5_F16, torch.float32: _lib.Y5_F32}[dtype]
     lib = _lib.lib()
-    _lib.check(lib.y5_mosaic_batch(C.c_void_p(table.data_ptr()), B, s, 114, C.c_void_p(out.data_ptr()), code, int(normalize and dtype != torch.uint8),
-                                   _lib.stream(dev)), lib)
+    _lib.check(lib.y5_mosaic_batch(C.c_void_p(table.data_ptr()), B, s, 114, C.c_void_p(out.data_ptr()), _lib.dtype_code(dtype),
+                                   int(normalize and dtype != torch.uint8), _lib.stream(dev)), lib)
     return out
+
+
+def _assemble(images, draws, s, hyp, sample_labels):
+    """Host half of a training batch: the filled y5_mosaic_batch job table, the (k, 6) targets of every image and, when the dataset has them, the
+    warped polygons with their images.  sample_labels(d, hw, pads, M, width, height) -> (pixel boxes (k, 5),) or (pixel boxes, polygons (k, ...))
+    of one mosaic or letterboxed image.  -> (jobs, labs, polys, inst)."""
+    B = len(draws)
+    use_hsv = bool(hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"])
+
+    def fill(j, d):
+        hw, pads, M, width, height = _fill_job(j, images, d, s)
+        return sample_labels(d, hw, pads, M, width, height), width, height
+
+    jobs = (_lib.MosaicJob * (B + sum(d.get("partner") is not None for d in draws)))()
+    labs, polys, inst, npart = [], [], [], 0
+    for b, d in enumerate(draws):
+        j = jobs[b]
+        parts, width, height = fill(j, d)
+        if d.get("partner") is not None:
+            # mixup (dataloaders.py:707-708; segment/augmentations.py:14-23): the partner mosaic is a job of its own behind the B rendered ones,
+            # its labels (and segments) are concatenated
+            parts2, _, _ = fill(jobs[B + npart], d["partner"])
+            j.mix_job, j.mix_r = B + npart + 1, float(d["mix_r"])
+            npart += 1
+            parts = [np.concatenate(p, 0) for p in zip(parts, parts2)]
+        _finish_job(j, d, use_hsv)
+        lb = _finish_labels(parts[0], d, width, height)
+        lb[:, 0] = b                                             # collate_fn (dataloaders.py:860-862; segment/dataloaders.py:299-300)
+        labs.append(lb)
+        for sg in parts[1:]:
+            polys.extend(sg)
+            inst.extend([b] * len(sg))
+    return jobs, labs, polys, inst
+
+
+def _targets(labs):
+    return torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
 
 
 def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normalize=False):
@@ -241,32 +337,8 @@ def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normaliz
     (k, 5) arrays [cls, xc, yc, w, h] normalised; draws: list (one per output image) of `draw_sample` dicts.
     Returns (imgs (B, 3, s, s) `dtype` RGB CHW, targets (nt, 6) float32 [image index in batch, cls, xc, yc, w, h])."""
     hyp = HYP_AUG if hyp is None else hyp
-    dev = images[0].device
-    B = len(draws)
-    labs = []
-    use_hsv = bool(hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"])
-    def fill(j, d):
-        hw, rects, pads, M, width, height = _fill_job(j, images, d, s)
-        return _labels(labels, d, hw, rects, M, width, height, s, pads), width, height
-
-    partners = [d for d in draws if d.get("partner") is not None]
-    jobs = (_lib.MosaicJob * (B + len(partners)))()
-    npart = 0
-    for b, d in enumerate(draws):
-        j = jobs[b]
-        t, width, height = fill(j, d)
-        if d.get("partner") is not None:   # mixup (dataloaders.py:707-708): the partner mosaic is a job of its own behind the B rendered ones
-            t2, _, _ = fill(jobs[B + npart], d["partner"])
-            j.mix_job, j.mix_r = B + npart + 1, float(d["mix_r"])
-            npart += 1
-            t = np.concatenate((t, t2), 0)
-        _finish_job(j, d, use_hsv)
-        lb = _finish_labels(t, d, width, height)
-        lb[:, 0] = b                                             # collate_fn (dataloaders.py:860-862)
-        labs.append(lb)
-    out = _render(jobs, B, s, dev, dtype, normalize)
-    targets = torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
-    return out, targets
+    jobs, labs, _, _ = _assemble(images, draws, s, hyp, lambda d, *geo: (_labels(labels, d, *geo, s),))
+    return _render(jobs, len(draws), s, images[0].device, dtype, normalize), _targets(labs)
 
 
 class MosaicLoader:
@@ -299,7 +371,8 @@ class MosaicLoader:
     def __len__(self):
         return (self.n_local + self.bs - 1) // self.bs
 
-    def __iter__(self):
+    def _epoch_order(self):
+        """This rank's image ids of the current epoch: the seeded shuffle, every `world`-th from `rank`, padded to the common length."""
         g = random.Random(self.seed + self.epoch)
         order = list(range(len(self.images)))
         g.shuffle(order)
@@ -307,11 +380,17 @@ class MosaicLoader:
             from .train_loop import pad_to_common
 
             order = pad_to_common(order[self.rank::self.world], len(self.images), self.world)
+        return order
+
+    def _batch(self, ids):
+        draws = [draw_sample(i, len(self.images), self.s, self.hyp) for i in ids]
+        imgs, targets = mosaic_batch(self.images, self.labels, draws, self.s, self.hyp, self.dtype, normalize=True)
+        return imgs, targets, [self.paths[i] for i in ids], None
+
+    def __iter__(self):
+        order = self._epoch_order()
         for b0 in range(0, len(order), self.bs):
-            ids = order[b0:b0 + self.bs]
-            draws = [draw_sample(i, len(self.images), self.s, self.hyp) for i in ids]
-            imgs, targets = mosaic_batch(self.images, self.labels, draws, self.s, self.hyp, self.dtype, normalize=True)
-            yield imgs, targets, [self.paths[i] for i in ids], None
+            yield self._batch(order[b0:b0 + self.bs])
         self.epoch += 1
 
 
@@ -329,45 +408,6 @@ def labels_from_segments(cls, segments):
     out[:, 1], out[:, 2] = (b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2
     out[:, 3], out[:, 4] = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
     return out
-
-
-def _perspective_draws(d, hyp, rng):
-    d["persp"] = (rng.uniform(-hyp["perspective"], hyp["perspective"]), rng.uniform(-hyp["perspective"], hyp["perspective"]))
-    d["angle"] = rng.uniform(-hyp["degrees"], hyp["degrees"])
-    d["scale"] = rng.uniform(1 - hyp["scale"], 1 + hyp["scale"])
-    d["shear"] = (rng.uniform(-hyp["shear"], hyp["shear"]), rng.uniform(-hyp["shear"], hyp["shear"]))
-    d["translate"] = (rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]), rng.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]))
-
-
-def draw_sample_seg(index, n_images, s, hyp, rng=random, np_rng=np.random):
-    """Random numbers of one sample in the order of the SEGMENTATION `__getitem__` (utils/segment/dataloaders.py), which is not `draw_sample`'s:
-    mosaic gate (:135); centre yc, xc (:239); three extra indices, NOT shuffled (:242); copy_paste draws nothing at p = 0 (:280);
-    random_perspective's eight (segment/augmentations.py:42-61); mixup gate (:141), partner = randint(0, n - 1) (:142), the partner mosaic's own
-    draws, np.random.beta (segment/augmentations.py:19); three HSV gains from numpy; flipud, fliplr gates (:212,219)."""
-    if hyp.get("copy_paste", 0.0):
-        raise NotImplementedError("SegMosaicLoader: copy_paste != 0 is not implemented")
-    if hyp["perspective"]:
-        raise NotImplementedError("SegMosaicLoader: perspective != 0 (cv2.warpPerspective) is not implemented")
-
-    def mosaic(i):
-        m = {"mosaic": True}
-        m["yc"], m["xc"] = (int(rng.uniform(-x, 2 * s + x)) for x in (-s // 2, -s // 2))
-        m["indices"] = [i, *rng.choices(range(n_images), k=3)]
-        _perspective_draws(m, hyp, rng)
-        return m
-
-    if rng.random() < hyp["mosaic"]:
-        d = mosaic(index)
-        if rng.random() < hyp["mixup"]:
-            d["partner"] = mosaic(rng.randint(0, n_images - 1))
-            d["mix_r"] = float(np_rng.beta(32.0, 32.0))
-    else:
-        d = {"mosaic": False, "indices": [index]}
-        _perspective_draws(d, hyp, rng)
-    d["hsv"] = np_rng.uniform(-1, 1, 3) * [hyp["hsv_h"], hyp["hsv_s"], hyp["hsv_v"]] + 1
-    d["flipud"] = rng.random() < hyp["flipud"]
-    d["fliplr"] = rng.random() < hyp["fliplr"]
-    return d
 
 
 _GRIDS = {}
@@ -401,35 +441,31 @@ def resample_segments(segs, n=1000):
     return out
 
 
-def _seg_labels(labels, segments, d, hw, rects, M, width, height, s, pads=None):
-    """Label half of one sample as utils/segment/augmentations.py:26-91 `random_perspective` computes it: tiles -> canvas pixels (xywhn2xyxy,
-    xyn2xy in float32), mosaic only: clip boxes and polygons to the canvas (:276-277), resample_segments(n = 1000), xy @ M.T, new box =
+def _xyn2xy(x, w, h, padw, padh):
+    """general.py:584-589 `xyn2xy` on (..., 2) float32 polygon points: normalised -> pixels."""
+    y = np.copy(x)
+    y[..., 0] = w * x[..., 0] + padw
+    y[..., 1] = h * x[..., 1] + padh
+    return y
+
+
+def _seg_labels(labels, segments, d, hw, pads, M, width, height, s):
+    """Label half of one sample as utils/segment/augmentations.py:26-91 `random_perspective` computes it: `_canvas_boxes`, the polygons likewise
+    (xyn2xy in float32; mosaic only: clipped to the canvas, :276-277), resample_segments(n = 1000), xy @ M.T, new box =
     segment2box(xy, width, height) (NOT the warped corners), box_candidates(area_thr = 0.01).
     -> ((k, 5) float32 [cls, x1, y1, x2, y2], (k, 1000, 2) float64 polygons) in output pixels."""
-    parts, segs, lens = [], [], []
-    for k, (i, (h, w), (x1a, y1a, _x2a, _y2a, x1b, y1b)) in enumerate(zip(d["indices"], hw, rects)):
-        lb = np.array(labels[i], dtype=np.float32).reshape(-1, 5).copy()
-        padw, padh = (x1a - x1b, y1a - y1b) if pads is None else pads[k]
-        if lb.size:
-            xy, half = lb[:, 1:3].copy(), lb[:, 3:5] / 2
-            lb[:, 1] = w * (xy[:, 0] - half[:, 0]) + padw
-            lb[:, 2] = h * (xy[:, 1] - half[:, 1]) + padh
-            lb[:, 3] = w * (xy[:, 0] + half[:, 0]) + padw
-            lb[:, 4] = h * (xy[:, 1] + half[:, 1]) + padh
-            if len(segments[i]) != len(lb):
-                raise ValueError(f"image {i}: {len(lb)} labels but {len(segments[i])} polygons")
-            sg = np.concatenate([np.asarray(g, dtype=np.float32).reshape(-1, 2) for g in segments[i]], 0)
-            y = np.copy(sg)                                            # xyn2xy (general.py:584-589) on all polygons of the tile at once
-            y[..., 0] = w * sg[..., 0] + padw
-            y[..., 1] = h * sg[..., 1] + padh
+    t, counts = _canvas_boxes(labels, d, hw, pads, s)
+    segs, lens = [], []
+    for i, (h, w), (padw, padh), k in zip(d["indices"], hw, pads, counts):
+        if k:
+            if len(segments[i]) != k:
+                raise ValueError(f"image {i}: {k} labels but {len(segments[i])} polygons")
+            # all polygons of the tile at once
+            y = _xyn2xy(np.concatenate([np.asarray(g, dtype=np.float32).reshape(-1, 2) for g in segments[i]], 0), w, h, padw, padh)
+            if d.get("mosaic", True):
+                np.clip(y, 0, 2 * s, out=y)
             segs.append(y)
             lens.extend(len(g) for g in segments[i])
-        parts.append(lb)
-    t = np.concatenate(parts, 0)
-    if d.get("mosaic", True):
-        np.clip(t[:, 1:], 0, 2 * s, out=t[:, 1:])
-        for x in segs:
-            np.clip(x, 0, 2 * s, out=x)
     n = len(t)
     if not n:
         return t, np.zeros((0, 1000, 2))
@@ -443,13 +479,7 @@ def _seg_labels(labels, segments, d, hw, rects, M, width, height, s, pads=None):
     new = np.stack((np.where(ins, x, np.inf).min(1), np.where(ins, y, np.inf).min(1), np.where(ins, x, -np.inf).max(1),
                     np.where(ins, y, -np.inf).max(1)), 1)
     new[~any_in] = 0.0
-    b1 = t[:, 1:5].T * d["scale"]
-    w1, h1 = b1[2] - b1[0], b1[3] - b1[1]
-    w2, h2 = new[:, 2] - new[:, 0], new[:, 3] - new[:, 1]
-    ar = np.maximum(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16))
-    keep = (w2 > 2) & (h2 > 2) & (w2 * h2 / (w1 * h1 + 1e-16) > 0.01) & (ar < 100)
-    t = t[keep]
-    t[:, 1:5] = new[keep]
+    t, keep = _box_candidates(t, new, d["scale"], 0.01)
     return t, xy[keep]
 
 
@@ -505,31 +535,15 @@ def _reorder(labs, order):
 def seg_mosaic_geometry(images, labels, segments, draws, s, hyp):
     """Host half of `seg_mosaic_batch`: the filled y5_mosaic_batch job table, the (k, 6) targets of every image in LABEL order, and the warped
     polygons (float64 output pixels) with their images -- the input of `polygon_masks`."""
-    B = len(draws)
-    use_hsv = bool(hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"])
+    return _assemble(images, draws, s, hyp, lambda d, *geo: _seg_labels(labels, segments, d, *geo, s))
 
-    def fill(j, d):
-        hw, rects, pads, M, width, height = _fill_job(j, images, d, s)
-        return _seg_labels(labels, segments, d, hw, rects, M, width, height, s, pads) + (width, height)
 
-    partners = [d for d in draws if d.get("partner") is not None]
-    jobs = (_lib.MosaicJob * (B + len(partners)))()
-    labs, polys, inst, npart = [], [], [], 0
-    for b, d in enumerate(draws):
-        j = jobs[b]
-        t, sg, width, height = fill(j, d)
-        if d.get("partner") is not None:                             # mixup (segment/augmentations.py:14-23): labels and segments concatenated
-            t2, sg2, _, _ = fill(jobs[B + npart], d["partner"])
-            j.mix_job, j.mix_r = B + npart + 1, float(d["mix_r"])
-            npart += 1
-            t, sg = np.concatenate((t, t2), 0), np.concatenate((sg, sg2), 0)
-        _finish_job(j, d, use_hsv)
-        lb = _finish_labels(t, d, width, height)
-        lb[:, 0] = b                                                 # collate_fn (segment/dataloaders.py:299-300)
-        labs.append(lb)
-        polys.extend(sg)
-        inst.extend([b] * len(sg))
-    return jobs, labs, polys, inst
+def _masks_and_targets(labs, polys, inst, B, s, mask_ratio, overlap, flips, dev):
+    """The mask half of a segmentation batch: ONE `polygon_masks` call, then, with overlap, the target rows of every image in its area order."""
+    masks, order = polygon_masks(polys, inst, B, s, s, mask_ratio, overlap, flips, dev)
+    if overlap:
+        labs = _reorder(labs, order)
+    return _targets(labs), masks
 
 
 def seg_mosaic_batch(images, labels, segments, draws, s, hyp=None, dtype=torch.uint8, normalize=False, overlap=True, mask_ratio=4):
@@ -543,10 +557,7 @@ def seg_mosaic_batch(images, labels, segments, draws, s, hyp=None, dtype=torch.u
     jobs, labs, polys, inst = seg_mosaic_geometry(images, labels, segments, draws, s, hyp)
     out = _render(jobs, B, s, dev, dtype, normalize)
     flips = [(bool(d["flipud"]), bool(d["fliplr"])) for d in draws]
-    masks, order = polygon_masks(polys, inst, B, s, s, mask_ratio, overlap, flips, dev)
-    if overlap:
-        labs = _reorder(labs, order)
-    targets = torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
+    targets, masks = _masks_and_targets(labs, polys, inst, B, s, mask_ratio, overlap, flips, dev)
     return out, targets, masks
 
 
@@ -562,21 +573,11 @@ class SegMosaicLoader(MosaicLoader):
         super().__init__(images, labels, img_size, batch_size, hyp, dtype, rank, world_size, seed, paths)
         self.segments, self.overlap, self.mask_ratio = segments, overlap, mask_ratio
 
-    def __iter__(self):
-        g = random.Random(self.seed + self.epoch)
-        order = list(range(len(self.images)))
-        g.shuffle(order)
-        if self.rank != -1:
-            from .train_loop import pad_to_common
-
-            order = pad_to_common(order[self.rank::self.world], len(self.images), self.world)
-        for b0 in range(0, len(order), self.bs):
-            ids = order[b0:b0 + self.bs]
-            draws = [draw_sample_seg(i, len(self.images), self.s, self.hyp) for i in ids]
-            imgs, targets, masks = seg_mosaic_batch(self.images, self.labels, self.segments, draws, self.s, self.hyp, self.dtype, normalize=True,
-                                                    overlap=self.overlap, mask_ratio=self.mask_ratio)
-            yield imgs, targets, [self.paths[i] for i in ids], None, masks
-        self.epoch += 1
+    def _batch(self, ids):
+        draws = [draw_sample_seg(i, len(self.images), self.s, self.hyp) for i in ids]
+        imgs, targets, masks = seg_mosaic_batch(self.images, self.labels, self.segments, draws, self.s, self.hyp, self.dtype, normalize=True,
+                                                overlap=self.overlap, mask_ratio=self.mask_ratio)
+        return imgs, targets, [self.paths[i] for i in ids], None, masks
 
 
 def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, normalize=False, overlap=True, mask_ratio=1, area=False):
@@ -595,24 +596,12 @@ def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, nor
     for b, i in enumerate(ids):
         d = dict(ident, indices=[i])
         j = jobs[b]
-        hw, rects, pads, _M, width, height = _fill_job(j, images, d, s)
+        hw, pads, _M, width, height = _fill_job(j, images, d, s)
         (h, w), (dw, dh) = hw[0], pads[0]
         h0, w0 = int(images[i].shape[0]), int(images[i].shape[1])
         shapes.append(((h0, w0), ((h / h0, w / w0), (dw, dh))))
-        lb = np.array(labels[i], dtype=np.float32).reshape(-1, 5).copy()
-        sgs = []
-        if lb.size:
-            xy, half = lb[:, 1:3].copy(), lb[:, 3:5] / 2
-            lb[:, 1] = w * (xy[:, 0] - half[:, 0]) + dw
-            lb[:, 2] = h * (xy[:, 1] - half[:, 1]) + dh
-            lb[:, 3] = w * (xy[:, 0] + half[:, 0]) + dw
-            lb[:, 4] = h * (xy[:, 1] + half[:, 1]) + dh
-        for sg in segments[i]:
-            sg = np.asarray(sg, dtype=np.float32)
-            y = np.copy(sg)
-            y[..., 0] = w * sg[..., 0] + dw
-            y[..., 1] = h * sg[..., 1] + dh
-            sgs.append(y)
+        lb, _ = _canvas_boxes(labels, d, hw, pads, s)
+        sgs = [_xyn2xy(np.asarray(sg, dtype=np.float32), w, h, dw, dh) for sg in segments[i]]
         if len(sgs) != len(lb):
             raise ValueError(f"image {i}: {len(lb)} labels but {len(sgs)} polygons")
         res = _finish_labels(lb, {"flipud": False, "fliplr": False}, width, height)
@@ -625,10 +614,7 @@ def seg_letterbox_batch(images, labels, segments, ids, s, dtype=torch.uint8, nor
                                    normalize)
     else:
         out = _render(jobs, B, s, dev, dtype, normalize)
-    masks, order = polygon_masks(polys, inst, B, s, s, mask_ratio, overlap, None, dev)
-    if overlap:
-        labs = _reorder(labs, order)
-    targets = torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
+    targets, masks = _masks_and_targets(labs, polys, inst, B, s, mask_ratio, overlap, None, dev)
     return out, targets, shapes, masks
 
 
@@ -696,9 +682,7 @@ def area_jobs(ims, sizes, places):
     jobs = (_lib.AreaJob * len(ims))()
     words, off, seen = [], 0, {}
     for j, im, (nh, nw), (top, left) in zip(jobs, ims, sizes, places):
-        if not (_lib.accepts(im) and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.stride(2) == 1 and im.stride(1) == 3):
-            raise ValueError("letterbox_area_batch: images must be uint8 (h, w, 3) device tensors with contiguous rows")
-        h0, w0 = int(im.shape[0]), int(im.shape[1])
+        h0, w0 = _check_image(im, "letterbox_area_batch")
         j.src, j.h0, j.w0, j.stride = im.data_ptr(), h0, w0, int(im.stride(0))
         j.nh, j.nw, j.top, j.left = int(nh), int(nw), int(top), int(left)
         if (nh, nw) == (h0, w0):
@@ -738,26 +722,14 @@ def letterbox_area_batch(ims, sizes, places, H, W, dtype=torch.uint8, normalize=
         if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > H or left + nw > W:
             raise ValueError(f"letterbox_area_batch: a {nh} x {nw} image at ({top}, {left}) does not fit the {H} x {W} canvas")
     jobs, tabs = area_jobs(ims, sizes, places)
-    table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev)
+    table = _lib.device_table(jobs, dev)
     tabs_d = torch.from_numpy(tabs).to(dev) if len(tabs) else None
     out = torch.empty((B, 3, H, W), dtype=dtype, device=dev)
-    code = {torch.uint8: _lib.Y5_U8, torch.float16: _lib.Y5_F16, torch.float32: _lib.Y5_F32}[dtype]
     lib = _lib.lib()
     _lib.check(lib.y5_letterbox_area_batch(C.c_void_p(table.data_ptr()), C.c_void_p(tabs_d.data_ptr()) if tabs_d is not None else None, len(tabs),
-                                           B, H, W, int(pad_value), C.c_void_p(out.data_ptr()), code, int(normalize and dtype != torch.uint8),
-                                           _lib.stream(dev)), lib)
+                                           B, H, W, int(pad_value), C.c_void_p(out.data_ptr()), _lib.dtype_code(dtype),
+                                           int(normalize and dtype != torch.uint8), _lib.stream(dev)), lib)
     return out
-
-
-def _xywhn2xyxy(x, w, h, padw, padh):
-    """ultralytics.utils.ops.xywhn2xyxy (call site utils/dataloaders.py:721), the reference's expressions: the TYPES of w, h, padw, padh decide
-    whether numpy evaluates them in float32 or float64, so the caller passes scalars made the way `letterbox` makes them."""
-    y = x.copy()
-    y[..., 0] = w * (x[..., 0] - x[..., 2] / 2) + padw
-    y[..., 1] = h * (x[..., 1] - x[..., 3] / 2) + padh
-    y[..., 2] = w * (x[..., 0] + x[..., 2] / 2) + padw
-    y[..., 3] = h * (x[..., 1] + x[..., 3] / 2) + padh
-    return y
 
 
 class ValLoader:
@@ -870,13 +842,9 @@ class ClassificationLoader:
     def __iter__(self):
         from .augmentations import classify_transform_batch
 
-        if self.shuffle:
-            order = torch.randperm(len(self.frames), generator=self._gen)
-            for b0 in range(0, len(self.frames), self.batch_size):
-                ids = order[b0:b0 + self.batch_size]
-                ims = [self.frames[i] for i in ids.tolist()]
-                yield classify_transform_batch(ims, self.imgsz, half=self.half, device=self.device), self.labels[ids.to(self.device)]
-            return
-        for b0 in range(0, len(self.frames), self.batch_size):
-            ims = self.frames[b0:b0 + self.batch_size]
-            yield classify_transform_batch(ims, self.imgsz, half=self.half, device=self.device), self.labels[b0:b0 + len(ims)]
+        n = len(self.frames)
+        order = torch.randperm(n, generator=self._gen) if self.shuffle else torch.arange(n)
+        for b0 in range(0, n, self.batch_size):
+            ids = order[b0:b0 + self.batch_size]
+            ims = [self.frames[i] for i in ids.tolist()]
+            yield classify_transform_batch(ims, self.imgsz, half=self.half, device=self.device), self.labels[ids.to(self.device)]

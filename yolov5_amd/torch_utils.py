@@ -22,7 +22,7 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
-from . import _lib as _libm, _state
+from . import _lib, _state
 
 
 def is_parallel(model):
@@ -106,7 +106,7 @@ class HipDDP(nn.Module):
             b.work = None
 
     def _launch(self, b):
-        if _libm.experimental("ddp_dry"):   # measurement aid (scripts/r5_ddp_reserve.py): bookkeeping only, no collective
+        if _lib.experimental("ddp_dry"):   # measurement aid (scripts/r5_ddp_reserve.py): bookkeeping only, no collective
             b.pending = -1
             return
         if self.world > 1 or self.avg_in_collective:  # (a 1-rank RCCL group still runs the collective: exercises the launch / wait path)
@@ -168,9 +168,6 @@ def scale_img(img, ratio=1.0, same_shape=False, gs=32, flip=None):
     """utils/torch_utils.py `scale_img` (+ the `x.flip(fi)` of models/yolo.py:276 folded in as `flip` = 2 | 3): bilinear resize of an NCHW float
     batch by `ratio` and padding with 0.447 to a multiple of `gs`, one `y5_scale_img` launch.  ratio == 1: the (flipped) image, unpadded, like
     the reference."""
-    import ctypes as C
-
-    from . import _lib
     if img.dtype not in (torch.float16, torch.float32) or img.dim() != 4 or not _lib.accepts(img):
         raise TypeError("scale_img: a float16 / float32 NCHW GPU batch is expected")
     img = img.contiguous()
@@ -262,20 +259,12 @@ class _HipMultiTensor(torch.optim.Optimizer):
 
     def _library(self):
         if self._lib is None:
-            from . import _lib
-
             self._lib = _lib.lib()
         return self._lib
 
     def _tables(self, ema_pairs):
         """Device-resident y5_mt_tensor table (rebuilt only when a pointer changes: .grad tensors are views of the engine's
         gradient arena and keep their address from step to step)."""
-        import ctypes as C
-
-        import numpy as np
-
-        from . import _lib
-
         name = type(self).__name__
         if len(self.param_groups) > 4:
             raise ValueError(f"{name}: at most 4 parameter groups")
@@ -302,7 +291,7 @@ class _HipMultiTensor(torch.optim.Optimizer):
             arr = (_lib.MtTensor * len(rows))()
             for r, (pp, gp, mp, ep, n, gi, _) in zip(arr, rows):
                 r.param, r.grad, r.mom, r.ema, r.n, r.group = pp, gp, mp or None, ep or None, n, gi
-            tab = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy()).to(dev)
+            tab = _lib.device_table(arr, dev)
             max_n = max(r[4] for r in rows)
             ws = _lib.workspace(self._library().y5_mt_workspace_bytes(len(rows), max_n), dev)
             stats = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -313,17 +302,11 @@ class _HipMultiTensor(torch.optim.Optimizer):
 
     @staticmethod
     def _stream(dev):
-        import ctypes as C
-
         return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
 
     @torch.no_grad()
     def step_fused(self, inv_scale=1.0, max_norm=0.0, ema=None, model=None):
         """One optimizer step; returns the device tensor [grad_norm, clip_coef, found_inf, -] when a norm pass ran, else None."""
-        import ctypes as C
-
-        from . import _lib
-
         if self._lib is None and any(not _lib.accepts(p) for g in self.param_groups for p in g["params"]):
             raise RuntimeError(f"{type(self).__name__}: parameters must live on the GPU (there is no CPU execution path)")
         lib = self._library()
@@ -388,8 +371,6 @@ class HipSGD(_HipMultiTensor):
                 raise ValueError("HipSGD: momentum / nesterov must be the same in every group")
 
     def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
-        from . import _lib
-
         lr, wd = self._group_vectors()
         g0 = self.param_groups[0]
         _lib.check(lib.y5_mt_sgd_step(C.c_void_p(tab.data_ptr()), n, max_n, (C.c_float * 4)(*lr), (C.c_float * 4)(*wd), float(g0["momentum"]),
@@ -501,8 +482,6 @@ class HipAdam(_HipStepCounted):
         return self._states(p, st, ("exp_avg", "exp_avg_sq"))
 
     def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
-        from . import _lib
-
         lr, wd = self._group_vectors()
         g0 = self.param_groups[0]
         step = self._step_tensor(tab.device)
@@ -545,8 +524,6 @@ class HipRMSprop(_HipStepCounted):
         return None, self._states(p, st, ("square_avg",))[0]
 
     def _update(self, lib, tab, second, n, max_n, inv_scale, stats, d, st):
-        from . import _lib
-
         lr, wd = self._group_vectors()
         g0 = self.param_groups[0]
         step = self._step_tensor(tab.device)
@@ -610,12 +587,6 @@ class ModelEMA:
     def lerp_rest(self, model, d, lib, stream, skip=()):
         """EMA of every float tensor of the state_dict that the optimizer kernel did not already update (buffers: BatchNorm
         running statistics; parameters without a gradient)."""
-        import ctypes as C
-
-        import numpy as np
-
-        from . import _lib
-
         pr = self._current_pairs(model)
         todo = [(s, e) for s, e in pr[2] if s.data_ptr() not in skip]
         if not todo:
@@ -629,7 +600,7 @@ class ModelEMA:
                 if s.dtype != torch.float32 or e.dtype != torch.float32 or not s.is_contiguous() or not e.is_contiguous():
                     raise TypeError("ModelEMA fused update: contiguous fp32 tensors only")
                 r.param, r.grad, r.mom, r.ema, r.n, r.group = s.data_ptr(), None, None, e.data_ptr(), s.numel(), 0
-            tab = (torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy()).to(todo[0][0].device), max(s.numel() for s, _ in todo))
+            tab = (_lib.device_table(arr, todo[0][0].device), max(s.numel() for s, _ in todo))
             pr[3][key] = tab
         _lib.check(lib.y5_mt_lerp(C.c_void_p(tab[0].data_ptr()), len(todo), tab[1], float(d), stream), lib)
         _state.bump_weights_epoch()
@@ -640,9 +611,7 @@ def classify_post(logits, labels=None, label_smoothing=0.0, want_probs=True):
     """One launch of y5_classify_post (csrc/classify.h) on a batch of logits (B, nc) fp16 / fp32: (top5 (B, 5) int32 -- the first min(5, nc)
     columns of argsort(1, descending=True), equal values by ascending index, unused columns -1; probs (B, nc) fp32 softmax or None; row_loss (B)
     fp32 cross-entropy with label smoothing per row, or None without labels).  No host synchronisation."""
-    import ctypes as C
-
-    if not (torch.is_tensor(logits) and _libm.accepts(logits)):
+    if not (torch.is_tensor(logits) and _lib.accepts(logits)):
         raise RuntimeError("yolov5_amd: classify_post needs logits on the GPU (there is no CPU execution path)")
     if logits.ndim != 2 or logits.dtype not in (torch.float16, torch.float32):
         raise ValueError(f"classify_post: expected (B, nc) fp16 / fp32 logits, got {logits.dtype} {tuple(logits.shape)}")
@@ -659,19 +628,17 @@ def classify_post(logits, labels=None, label_smoothing=0.0, want_probs=True):
             raise ValueError(f"classify_post: expected {B} labels, got {tuple(lab.shape)}")
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    lib = _libm.lib()
-    rc = lib.y5_classify_post(p(logits), _libm.Y5_F16 if logits.dtype == torch.float16 else _libm.Y5_F32, B, nc, logits.stride(0), p(lab),
-                              float(label_smoothing), p(top5), p(probs), p(loss), _libm.stream(dev))
-    _libm.check(rc, lib)
+    lib = _lib.lib()
+    rc = lib.y5_classify_post(p(logits), _lib.Y5_F16 if logits.dtype == torch.float16 else _lib.Y5_F32, B, nc, logits.stride(0), p(lab),
+                              float(label_smoothing), p(top5), p(probs), p(loss), _lib.stream(dev))
+    _lib.check(rc, lib)
     return top5, probs, loss
 
 
 def classify_ce_bwd(logits, labels, label_smoothing, grad_rows):
     """One launch of y5_classify_ce_bwd (csrc/classify_train.h): dlogits (B, nc) in the logits' dtype for the per-row cross-entropy losses of
     classify_post, `grad_rows` (B) being the gradient that reaches those rows.  No host synchronisation."""
-    import ctypes as C
-
-    if not (torch.is_tensor(logits) and _libm.accepts(logits)):
+    if not (torch.is_tensor(logits) and _lib.accepts(logits)):
         raise RuntimeError("yolov5_amd: classify_ce_bwd needs logits on the GPU (there is no CPU execution path)")
     if logits.stride(1) != 1:
         logits = logits.contiguous()
@@ -683,10 +650,10 @@ def classify_ce_bwd(logits, labels, label_smoothing, grad_rows):
         raise ValueError(f"classify_ce_bwd: expected {B} labels and row gradients, got {tuple(lab.shape)}, {tuple(g.shape)}")
     out = torch.empty((B, nc), dtype=logits.dtype, device=dev)
     p = lambda t: C.c_void_p(t.data_ptr())
-    lib = _libm.lib()
-    rc = lib.y5_classify_ce_bwd(p(logits), _libm.Y5_F16 if logits.dtype == torch.float16 else _libm.Y5_F32, B, nc, logits.stride(0), p(lab),
-                                float(label_smoothing), p(g), p(out), nc, _libm.stream(dev))
-    _libm.check(rc, lib)
+    lib = _lib.lib()
+    rc = lib.y5_classify_ce_bwd(p(logits), _lib.Y5_F16 if logits.dtype == torch.float16 else _lib.Y5_F32, B, nc, logits.stride(0), p(lab),
+                                float(label_smoothing), p(g), p(out), nc, _lib.stream(dev))
+    _lib.check(rc, lib)
     return out
 
 
