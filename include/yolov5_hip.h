@@ -708,6 +708,24 @@ typedef struct {
 int y5_mosaic_batch(const y5_mosaic_job* jobs_dev, int B, int S, int pad_value, void* dst, int dst_dtype, int div255, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * y5_paste_planes / y5_mosaic_batch_paste -- the image half of utils/augmentations.py:200-222 `copy_paste` (hyp['copy_paste']), which both
+ * `load_mosaic`s call on the 2s x 2s canvas after the clip and before random_perspective (utils/dataloaders.py:842,
+ * utils/segment/dataloaders.py:280): cv2.drawContours(im_new, [segment.astype(np.int32)], -1, (1, 1, 1), cv2.FILLED) for every ACCEPTED
+ * polygon (:216), then `im[flip(im_new)] = flip(im)[flip(im_new)]` (:218-220).  The sample, the bbox_ioa test and the labels are the host's
+ * (yolov5_amd/dataloaders.py `_copy_paste`).  Kernels: csrc/copy_paste.h, csrc/augment.hip.
+ * y5_paste_planes: pts (poly_off[n_poly], 2) int32 canvas points, polygon q owns points poly_off[q] .. poly_off[q + 1] and belongs to plane
+ * poly_plane[q] (ASCENDING; a plane may own no polygon).  planes: (n_planes, S2, ceil(S2 / 32)) uint32, bit x & 31 of word x >> 5 of row y = the
+ * UN-FLIPPED union of the filled polygons of the plane (the fill of cv2.fillPoly, as y5_polygon_masks); every word is written, bits at
+ * x >= S2 are 0.  S2 <= 8160.  One launch, no atomics on memory.
+ * y5_mosaic_batch_paste: y5_mosaic_batch with the paste.  job_plane: DEVICE array of n_jobs >= B ints, one per job of the table (the mixup
+ * partners behind the first B included): the job's plane (S2 = 2 S), or -1 for a job that pastes nothing and for every job of the letterbox
+ * branch (job.canvas > 0; a plane given there is ignored).  With every entry -1 the output is y5_mosaic_batch's.
+ * ------------------------------------------------------------------------------------------------------- */
+int y5_paste_planes(const int* pts, const int* poly_off, const int* poly_plane, int n_poly, int n_planes, int S2, unsigned* planes, void* stream);
+int y5_mosaic_batch_paste(const y5_mosaic_job* jobs_dev, int n_jobs, const int* job_plane, const unsigned* planes, int B, int S, int pad_value,
+                          void* dst, int dst_dtype, int div255, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * y5_polygon_masks -- the mask half of the segmentation input pipeline for a whole batch: utils/segment/dataloaders.py:180-199
  * (`polygons2masks_overlap` / `polygons2masks` of ultralytics.data.utils, i.e. per instance np.asarray(polygon, int32) ->
  * cv2.fillPoly(zeros(H, W), [pts], 1) -> cv2.resize to (H / ratio, W / ratio)), the mask flips of :212-223 and collate_fn's

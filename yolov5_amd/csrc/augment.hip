@@ -22,12 +22,15 @@
 #include "y5_host.h"
 #include "resize_u8.h"
 #include "seg_data.h"   // y5_polygon_masks: the mask half of the segmentation input pipeline
+#include "copy_paste.h" // y5_paste_planes: the bit planes of the copy-paste augmentation (utils/augmentations.py:200-222)
 
 namespace {
 struct AugParams {
   const y5_mosaic_job* jobs;
   void* dst;
   int B, S, dst_dtype, div255, pad;
+  const int* job_plane;     // PASTE only: plane of every job of the table (-1: none), and the planes y5_paste_planes made
+  const unsigned* planes;
 };
 
 __device__ inline long long sat_int(double v) {  // saturate_cast<int>(double): cvRound = round half to even, clamped
@@ -35,10 +38,20 @@ __device__ inline long long sat_int(double v) {  // saturate_cast<int>(double): 
   return r < -2147483648.0 ? -2147483648LL : (r > 2147483647.0 ? 2147483647LL : (long long)r);
 }
 
-// pixel (yy, xx) of the virtual canvas: 2s x 2s for a mosaic, s x s for the letterboxed single image of the non-mosaic branch (job.canvas)
-__device__ inline void canvas_pixel(const y5_mosaic_job& j, const ResizeGeom* g, int S2, int pad, int yy, int xx, int out[3]) {
+// pixel (yy, xx) of the virtual canvas: 2s x 2s for a mosaic, s x s for the letterboxed single image of the non-mosaic branch (job.canvas).
+// PASTE, bits = the job's copy-paste plane (copy_paste.h) or null: `im[i] = result[i]` of utils/augmentations.py:218-220 -- where the raster of
+// the accepted polygons covers the mirror position (yy, S2 - 1 - xx), the pixel is the UN-PASTED canvas pixel there (no recursion: `result` is
+// taken before the assignment).
+template <bool PASTE>
+__device__ inline void canvas_pixel(const y5_mosaic_job& j, const ResizeGeom* g, int S2, int pad, const unsigned* bits, int yy, int xx, int out[3]) {
   out[0] = out[1] = out[2] = pad;
   if (yy < 0 || xx < 0 || yy >= S2 || xx >= S2) return;
+  if constexpr (PASTE) {
+    if (bits) {
+      const int xm = S2 - 1 - xx;
+      if ((bits[(size_t)yy * ((S2 + 31) >> 5) + (xm >> 5)] >> (xm & 31)) & 1u) xx = xm;
+    }
+  }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {  // later tiles overwrite earlier ones where rectangles touch (assignment order of load_mosaic)
     if (j.src[t] && yy >= j.y1a[t] && yy < j.y2a[t] && xx >= j.x1a[t] && xx < j.x2a[t])
@@ -89,7 +102,8 @@ __device__ inline void hsv2bgr_u8(int h8, int s8, int v8, int out[3]) {  // HSV2
 }  // namespace
 
 // the warped canvas of job j at output pixel (x, y): WarpAffineInvoker's fixed-point source position (5 fractional bits) and 15-bit bilinear weights
-__device__ inline void warp_pixel(const y5_mosaic_job& j, int S, int pad, int x, int y, int bgr[3]) {
+template <bool PASTE>
+__device__ inline void warp_pixel(const y5_mosaic_job& j, int S, int pad, const unsigned* bits, int x, int y, int bgr[3]) {
   ResizeGeom g[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) g[t] = resize_geom(j.h0[t], j.w0[t], j.rh[t], j.rw[t]);
@@ -102,10 +116,10 @@ __device__ inline void warp_pixel(const y5_mosaic_job& j, int S, int pad, int x,
   const int sx = (int)sxl, sy = (int)syl, fx = (int)(X & 31), fy = (int)(Y & 31);
   int p00[3], p01[3], p10[3], p11[3];
   const int S2 = j.canvas > 0 ? j.canvas : 2 * S;
-  canvas_pixel(j, g, S2, pad, sy, sx, p00);
-  canvas_pixel(j, g, S2, pad, sy, sx + 1, p01);
-  canvas_pixel(j, g, S2, pad, sy + 1, sx, p10);
-  canvas_pixel(j, g, S2, pad, sy + 1, sx + 1, p11);
+  canvas_pixel<PASTE>(j, g, S2, pad, bits, sy, sx, p00);
+  canvas_pixel<PASTE>(j, g, S2, pad, bits, sy, sx + 1, p01);
+  canvas_pixel<PASTE>(j, g, S2, pad, bits, sy + 1, sx, p10);
+  canvas_pixel<PASTE>(j, g, S2, pad, bits, sy + 1, sx + 1, p11);
   const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -114,6 +128,14 @@ __device__ inline void warp_pixel(const y5_mosaic_job& j, int S, int pad, int x,
   }
 }
 
+// the copy-paste plane of job `job` of the table: only a mosaic (canvas 2S x 2S) has one
+__device__ inline const unsigned* paste_bits(const AugParams& p, int job) {
+  const int pl = p.job_plane[job];
+  return pl >= 0 && p.jobs[job].canvas <= 0 ? p.planes + (size_t)pl * (2 * p.S) * ((2 * p.S + 31) >> 5) : nullptr;
+}
+
+// PASTE = false is the launch without planes (y5_mosaic_batch): its own instantiation, which never looks at job_plane / planes
+template <bool PASTE>
 __global__ __launch_bounds__(256)
 void y5_mosaic_kernel(const AugParams p) {
   const int b = blockIdx.y;
@@ -124,10 +146,10 @@ void y5_mosaic_kernel(const AugParams p) {
   const y5_mosaic_job& j = p.jobs[b];
   const int y = j.flipud ? S - 1 - oy : oy, x = j.fliplr ? S - 1 - ox : ox;   // np.flipud / np.fliplr of the warped image
   int bgr[3];
-  warp_pixel(j, S, p.pad, x, y, bgr);
+  warp_pixel<PASTE>(j, S, p.pad, PASTE ? paste_bits(p, b) : nullptr, x, y, bgr);
   if (j.mix_job > 0) {   // utils/augmentations.py:225-233 mixup: (im * r + im2 * (1 - r)).astype(np.uint8) on the two warped mosaics, in double
     int b2[3];
-    warp_pixel(p.jobs[j.mix_job - 1], S, p.pad, x, y, b2);
+    warp_pixel<PASTE>(p.jobs[j.mix_job - 1], S, p.pad, PASTE ? paste_bits(p, j.mix_job - 1) : nullptr, x, y, b2);
 #pragma unroll
     for (int c = 0; c < 3; ++c) bgr[c] = (int)((double)bgr[c] * j.mix_r + (double)b2[c] * (1.0 - j.mix_r));
   }
@@ -158,13 +180,27 @@ void y5_mosaic_kernel(const AugParams p) {
   }
 }
 
-extern "C" int y5_mosaic_batch(const y5_mosaic_job* jobs_dev, int B, int S, int pad_value, void* dst, int dst_dtype, int div255, void* stream_) {
+template <bool PASTE>
+static int mosaic_launch(const char* who, const y5_mosaic_job* jobs_dev, const int* job_plane, const unsigned* planes, int B, int S, int pad_value,
+                         void* dst, int dst_dtype, int div255, void* stream_) {
   if (!jobs_dev || !dst) return y5_fail(Y5_ERR_BAD_ARG, "mosaic_batch: null pointer");
   if (B < 1 || B > 65535 || S < 2 || S > 16384 || pad_value < 0 || pad_value > 255) return y5_fail(Y5_ERR_BAD_ARG, "mosaic_batch: bad B / S / pad value");
   if (dst_dtype != Y5_U8 && dst_dtype != Y5_F16 && dst_dtype != Y5_F32) return y5_fail(Y5_ERR_BAD_ARG, "mosaic_batch: dst dtype must be u8, f16 or f32");
   AugParams p{};
   p.jobs = jobs_dev; p.dst = dst; p.B = B; p.S = S; p.dst_dtype = dst_dtype; p.div255 = div255; p.pad = pad_value;
+  p.job_plane = job_plane; p.planes = planes;
   const long long n = (long long)S * S;
-  hipLaunchKernelGGL(y5_mosaic_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, static_cast<hipStream_t>(stream_), p);
-  return y5_check_launch("y5_mosaic_batch");
+  hipLaunchKernelGGL(y5_mosaic_kernel<PASTE>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, static_cast<hipStream_t>(stream_), p);
+  return y5_check_launch(who);
+}
+
+extern "C" int y5_mosaic_batch(const y5_mosaic_job* jobs_dev, int B, int S, int pad_value, void* dst, int dst_dtype, int div255, void* stream_) {
+  return mosaic_launch<false>("y5_mosaic_batch", jobs_dev, nullptr, nullptr, B, S, pad_value, dst, dst_dtype, div255, stream_);
+}
+
+extern "C" int y5_mosaic_batch_paste(const y5_mosaic_job* jobs_dev, int n_jobs, const int* job_plane, const unsigned* planes, int B, int S, int pad_value,
+                                     void* dst, int dst_dtype, int div255, void* stream_) {
+  if (!job_plane || n_jobs < B) return y5_fail(Y5_ERR_BAD_ARG, "mosaic_batch_paste: job_plane must cover the B rendered jobs and their mixup partners");
+  if (!planes) return y5_fail(Y5_ERR_BAD_ARG, "mosaic_batch_paste: null planes");
+  return mosaic_launch<true>("y5_mosaic_batch_paste", jobs_dev, job_plane, planes, B, S, pad_value, dst, dst_dtype, div255, stream_);
 }

@@ -127,12 +127,14 @@ __device__ inline bool make_edge(int W, int H, int X0, int Y0, int X1, int Y1, E
   return true;
 }
 
-// Line(img, p1, p2, color, 8): LineIterator(8-connected, left to right) after clipLine; ORs the pixels into the plane
-__device__ inline void draw_line(unsigned* plane, int W32, int W, int H, int X0, int Y0, int X1, int Y1) {
+// Line(img, p1, p2, color, 8): LineIterator(8-connected, left to right) after clipLine; ORs the pixels that fall on the rows [y_lo, y_hi) into
+// `rows`, the bit rows of that window (`pitch` words each, the first one is row y_lo).  The whole plane is the window [0, H).
+__device__ inline void draw_line(unsigned* rows, int pitch, int W, int H, int y_lo, int y_hi, int X0, int Y0, int X1, int Y1) {
   long long ax = X0, ay = Y0, bx = X1, by = Y1;
   if (!inside(W, H, ax, ay) || !inside(W, H, bx, by)) {
     if (!clip_line(W, H, ax, ay, bx, by)) return;
   }
+  if ((ay < y_lo && by < y_lo) || (ay >= y_hi && by >= y_hi)) return;   // the line does not reach the window
   int dx = (int)(bx - ax), dy = (int)(by - ay), x = (int)ax, y = (int)ay, sy = 1;
   if (dx < 0) { dx = -dx; dy = -dy; x = (int)bx; y = (int)by; }
   if (dy < 0) { dy = -dy; sy = -1; }
@@ -141,11 +143,43 @@ __device__ inline void draw_line(unsigned* plane, int W32, int W, int H, int X0,
   int err = dx - (dy + dy);
   const int plus = dx + dx, minus = -(dy + dy);
   for (int k = 0; k <= dx; ++k) {
-    if (x >= 0 && x < W && y >= 0 && y < H) lds_or(&plane[y * W32 + (x >> 5)], 1u << (x & 31));   // (always true after the clip; the guard is the bound)
+    // (x and the plane's rows are always in range after the clip; the guard is the bound)
+    if (x >= 0 && x < W && y >= y_lo && y < y_hi) lds_or(&rows[(y - y_lo) * pitch + (x >> 5)], 1u << (x & 31));
     const bool neg = err < 0;
     err += minus + (neg ? plus : 0);
     if (vert) { y += sy; x += neg ? 1 : 0; }
     else { x += 1; y += neg ? sy : 0; }
+  }
+}
+
+// The crossings of edge e with the rows [y_lo, y_hi) of the same window: step 1 toggles the bit at column r + 1, step 3 ORs the bit at r.
+__device__ inline void toggle_crossings(unsigned* rows, int pitch, int W, const Edge& e, int y_lo, int y_hi) {
+  const int ya = e.y0 > y_lo ? e.y0 : y_lo, yb = e.y1 < y_hi ? e.y1 : y_hi;
+  for (int y = ya; y < yb; ++y) {
+    const long long c = ((e.x + (long long)((long long)y - e.y0) * e.dx) >> XY_SHIFT) + 1;
+    if (c < W) {
+      const int cc = c < 0 ? 0 : (int)c;
+      lds_xor(&rows[(y - y_lo) * pitch + (cc >> 5)], 1u << (cc & 31));
+    }
+  }
+}
+__device__ inline void or_crossings(unsigned* rows, int pitch, int W, const Edge& e, int y_lo, int y_hi) {
+  const int ya = e.y0 > y_lo ? e.y0 : y_lo, yb = e.y1 < y_hi ? e.y1 : y_hi;
+  for (int y = ya; y < yb; ++y) {
+    const long long r = (e.x + (long long)((long long)y - e.y0) * e.dx) >> XY_SHIFT;
+    if (r >= 0 && r < W) lds_or(&rows[(y - y_lo) * pitch + (int)(r >> 5)], 1u << (int)(r & 31));
+  }
+}
+
+// step 2 on one row of W32 words: the toggles become the parity of the toggles to their left (inclusive)
+__device__ inline void prefix_xor_row(unsigned* row, int W32) {
+  unsigned carry = 0u;
+  for (int k = 0; k < W32; ++k) {
+    unsigned v = row[k];
+    v ^= v << 1; v ^= v << 2; v ^= v << 4; v ^= v << 8; v ^= v << 16;
+    if (carry) v = ~v;
+    carry = v >> 31;
+    row[k] = v;
   }
 }
 
@@ -176,40 +210,20 @@ void y5_polygon_raster_kernel(const segdata::Params p) {
     const int j = i == 0 ? np - 1 : i - 1;
     Edge e;
     if (!make_edge(W, H, trunc_i32(xy[2 * j]), trunc_i32(xy[2 * j + 1]), trunc_i32(xy[2 * i]), trunc_i32(xy[2 * i + 1]), e)) continue;
-    const int ya = e.y0 > 0 ? e.y0 : 0, yb = e.y1 < H ? e.y1 : H;
-    for (int y = ya; y < yb; ++y) {
-      const long long c = ((e.x + (long long)((long long)y - e.y0) * e.dx) >> XY_SHIFT) + 1;
-      if (c < W) {
-        const int cc = c < 0 ? 0 : (int)c;
-        lds_xor(&plane[y * W32 + (cc >> 5)], 1u << (cc & 31));
-      }
-    }
+    toggle_crossings(plane, W32, W, e, 0, H);
   }
   __syncthreads();
   // 2. prefix xor along every row
-  for (int y = tid; y < H; y += NT) {
-    unsigned carry = 0u;
-    for (int k = 0; k < W32; ++k) {
-      unsigned v = plane[y * W32 + k];
-      v ^= v << 1; v ^= v << 2; v ^= v << 4; v ^= v << 8; v ^= v << 16;
-      if (carry) v = ~v;
-      carry = v >> 31;
-      plane[y * W32 + k] = v;
-    }
-  }
+  for (int y = tid; y < H; y += NT) prefix_xor_row(plane + y * W32, W32);
   __syncthreads();
   // 3. the crossings' own pixels and the edges' lines
   for (int i = tid; i < np; i += NT) {
     const int j = i == 0 ? np - 1 : i - 1;
     const int X0 = trunc_i32(xy[2 * j]), Y0 = trunc_i32(xy[2 * j + 1]), X1 = trunc_i32(xy[2 * i]), Y1 = trunc_i32(xy[2 * i + 1]);
-    draw_line(plane, W32, W, H, X0, Y0, X1, Y1);
+    draw_line(plane, W32, W, H, 0, H, X0, Y0, X1, Y1);
     Edge e;
     if (!make_edge(W, H, X0, Y0, X1, Y1, e)) continue;
-    const int ya = e.y0 > 0 ? e.y0 : 0, yb = e.y1 < H ? e.y1 : H;
-    for (int y = ya; y < yb; ++y) {
-      const long long r = (e.x + (long long)((long long)y - e.y0) * e.dx) >> XY_SHIFT;
-      if (r >= 0 && r < W) lds_or(&plane[y * W32 + (int)(r >> 5)], 1u << (int)(r & 31));
-    }
+    or_crossings(plane, W32, W, e, 0, H);
   }
   __syncthreads();
   // 4. cv2.resize(mask, (w, h)) -> bits, area

@@ -23,13 +23,19 @@ The host rules they share, each written once:
     geometry     `_resized_hw` (load_image; every loader), `_tile_rects`, `_affine`, `_invert_affine`, `_fill_job` (one y5_mosaic_batch job:
                  both training loaders and `seg_letterbox_batch`), `_check_image` (the image contract, also `area_jobs`)
     labels       `_xywhn2xyxy` (`_canvas_boxes`, `ValLoader`), `_canvas_boxes` (`_labels`, `_seg_labels`, `seg_letterbox_batch`), `_xyn2xy`
-                 (`_seg_labels`, `seg_letterbox_batch`), `_box_candidates` (`_labels`, `_seg_labels`), `_finish_labels` (every detection and
+                 (`_canvas_stage`, `seg_letterbox_batch`), `_canvas_stage` + `_warp_polygons` (`_labels` with polygons, `_seg_labels`),
+                 `_box_candidates` (`_labels`, `_warp_polygons`), `_finish_labels` (every detection and
                  segmentation loader)
     batches      `_assemble` (the job and label loop of `mosaic_batch` and `seg_mosaic_geometry`: mixup partners, HSV tables, batch index),
-                 `_render` (the y5_mosaic_batch launch: both training loaders, `seg_letterbox_batch`), `_masks_and_targets` (both segmentation
+                 `_render` (the y5_mosaic_batch / y5_mosaic_batch_paste launch: both training loaders, `seg_letterbox_batch`), `_masks_and_targets` (both segmentation
                  batch functions), `_targets`
     epochs       `MosaicLoader._epoch_order` (seeded shuffle, rank stride, padding); `SegMosaicLoader` overrides only `_batch`
-Not covered: reading images and label files from disk and the caches, image_weights, rect batches for TRAINING, collate_fn4, copy_paste,
+Copy-paste (hyp['copy_paste'], utils/augmentations.py:200-222; both loaders, mosaics only, mixup partners included): `_mosaic_draws` draws its one
+random.sample at the reference's position (needs `counts`, the polygons of every image), `_copy_paste` restates the label half (bbox_ioa
+against the growing label array) in `_canvas_stage`, `paste_planes` (ONE y5_paste_planes launch, csrc/copy_paste.h) fills the accepted
+original polygons into a bit plane per pasting job and `_render` then launches y5_mosaic_batch_paste, which redirects the covered canvas
+pixels to their mirror position.  `MosaicLoader(segments=...)` also takes random_perspective's `use_segments` branch (`_warp_polygons`).
+Not covered: reading images and label files from disk and the caches, image_weights, rect batches for TRAINING, collate_fn4,
 albumentations, perspective != 0."""
 from __future__ import annotations
 
@@ -57,23 +63,31 @@ def _perspective_draws(d, hyp, rng):
     return d
 
 
-def _mosaic_draws(index, n_images, s, hyp, rng, shuffle):
-    """Draws of one mosaic (load_mosaic -> random_perspective): centre yc, xc; three extra indices, shuffled with `index` when `shuffle`; the eight."""
+def _mosaic_draws(index, n_images, s, hyp, rng, shuffle, counts=None):
+    """Draws of one mosaic (load_mosaic -> copy_paste -> random_perspective): centre yc, xc; three extra indices, shuffled with `index` when
+    `shuffle`; copy_paste's ONE draw, random.sample(range(n), k=round(p * n)) under its `if p and n` gate (augmentations.py:206-209), n = the
+    polygons of the four tiles (`counts`: the number of polygons of every dataset image); the eight."""
     d = {"mosaic": True}
     d["yc"], d["xc"] = (int(rng.uniform(-x, 2 * s + x)) for x in (-s // 2, -s // 2))
     d["indices"] = [index, *rng.choices(range(n_images), k=3)]
     if shuffle:
         rng.shuffle(d["indices"])
+    p = hyp.get("copy_paste", 0.0)
+    if p and counts is not None:
+        n = sum(int(counts[i]) for i in d["indices"])
+        if n:
+            d["paste"] = rng.sample(range(n), k=round(p * n))
     return _perspective_draws(d, hyp, rng)
 
 
-def _draw_sample(index, n_images, s, hyp, rng, np_rng, shuffle, partner):
-    """The draw order both `__getitem__`s share: mosaic gate; the mosaic's draws; mixup gate, `partner()` index, the partner mosaic's own draws,
-    np.random.beta in mixup(); three HSV gains from numpy (augmentations.py:72); flipud, fliplr gates."""
+def _draw_sample(index, n_images, s, hyp, rng, np_rng, shuffle, partner, counts=None):
+    """The draw order both `__getitem__`s share: mosaic gate; the mosaic's draws; mixup gate, `partner()` index, the partner mosaic's own draws
+    (its own copy_paste sample included), np.random.beta in mixup(); three HSV gains from numpy (augmentations.py:72); flipud, fliplr gates.
+    copy_paste runs in load_mosaic only: the letterbox branch draws nothing for it."""
     if rng.random() < hyp["mosaic"]:
-        d = _mosaic_draws(index, n_images, s, hyp, rng, shuffle)
+        d = _mosaic_draws(index, n_images, s, hyp, rng, shuffle, counts)
         if rng.random() < hyp["mixup"]:
-            d["partner"] = _mosaic_draws(partner(), n_images, s, hyp, rng, shuffle)
+            d["partner"] = _mosaic_draws(partner(), n_images, s, hyp, rng, shuffle, counts)
             d["mix_r"] = float(np_rng.beta(32.0, 32.0))
     else:   # letterbox branch (dataloaders.py:710-733): the next draws are random_perspective's; no mixup gate on this side
         d = _perspective_draws({"mosaic": False, "indices": [index]}, hyp, rng)
@@ -83,26 +97,28 @@ def _draw_sample(index, n_images, s, hyp, rng, np_rng, shuffle, partner):
     return d
 
 
-def draw_sample(index, n_images, s, hyp, rng=random, np_rng=np.random):
+def draw_sample(index, n_images, s, hyp, rng=random, np_rng=np.random, counts=None):
     """Random numbers of one sample in the reference's order: mosaic gate (dataloaders.py:701); centre yc, xc (:802); three extra
-    indices + shuffle (:803-804); perspective x2, angle, scale, shear x2, translate x2 (augmentations.py:135-156); mixup gate
+    indices + shuffle (:803-804); copy_paste's sample (:842, augmentations.py:209) when hyp['copy_paste'] and `counts` -- the number of
+    polygons of every dataset image -- are given; perspective x2, angle, scale, shear x2, translate x2 (augmentations.py:135-156); mixup gate
     (dataloaders.py:707), partner = random.choice(indices) (:708); three HSV gains from numpy (augmentations.py:72); flipud, fliplr gates
-    (dataloaders.py:747,753)."""
+    (dataloaders.py:747,753).  Without counts the dataset has no polygons: copy_paste's `if p and n` gate then draws nothing."""
     if hyp["perspective"]:
         raise NotImplementedError("MosaicLoader: perspective != 0 (cv2.warpPerspective) is not implemented")
-    return _draw_sample(index, n_images, s, hyp, rng, np_rng, True, lambda: rng.choice(range(n_images)))
+    return _draw_sample(index, n_images, s, hyp, rng, np_rng, True, lambda: rng.choice(range(n_images)), counts)
 
 
-def draw_sample_seg(index, n_images, s, hyp, rng=random, np_rng=np.random):
+def draw_sample_seg(index, n_images, s, hyp, rng=random, np_rng=np.random, counts=None):
     """Random numbers of one sample in the order of the SEGMENTATION `__getitem__` (utils/segment/dataloaders.py), which is not `draw_sample`'s:
-    mosaic gate (:135); centre yc, xc (:239); three extra indices, NOT shuffled (:242); copy_paste draws nothing at p = 0 (:280);
-    random_perspective's eight (segment/augmentations.py:42-61); mixup gate (:141), partner = randint(0, n - 1) (:142), the partner mosaic's own
-    draws, np.random.beta (segment/augmentations.py:19); three HSV gains from numpy; flipud, fliplr gates (:212,219)."""
-    if hyp.get("copy_paste", 0.0):
-        raise NotImplementedError("SegMosaicLoader: copy_paste != 0 is not implemented")
+    mosaic gate (:135); centre yc, xc (:239); three extra indices, NOT shuffled (:242); copy_paste's sample (:280, augmentations.py:209; nothing
+    at p = 0), which needs `counts`, the number of polygons of every dataset image; random_perspective's eight
+    (segment/augmentations.py:42-61); mixup gate (:141), partner = randint(0, n - 1) (:142), the partner mosaic's own draws, np.random.beta
+    (segment/augmentations.py:19); three HSV gains from numpy; flipud, fliplr gates (:212,219)."""
+    if hyp.get("copy_paste", 0.0) and counts is None:
+        raise NotImplementedError("draw_sample_seg: copy_paste != 0 needs counts, the number of polygons of every image")
     if hyp["perspective"]:
         raise NotImplementedError("SegMosaicLoader: perspective != 0 (cv2.warpPerspective) is not implemented")
-    return _draw_sample(index, n_images, s, hyp, rng, np_rng, False, lambda: rng.randint(0, n_images - 1))
+    return _draw_sample(index, n_images, s, hyp, rng, np_rng, False, lambda: rng.randint(0, n_images - 1), counts)
 
 
 def _resized_hw(h0, w0, s):
@@ -197,10 +213,90 @@ def _box_candidates(t, new, scale, area_thr):
     return t, keep
 
 
-def _labels(labels, d, hw, pads, M, width, height, s):
-    """Label half of the sample up to random_perspective: `_canvas_boxes`, corners through M + hull + clip + box_candidates(area_thr = 0.10)
-    (augmentations.py:193-209) -> (k, 5) [cls, x1, y1, x2, y2] in output pixels."""
-    t, _ = _canvas_boxes(labels, d, hw, pads, s)
+def _bbox_ioa(box1, box2, eps=1e-7):
+    """ultralytics.utils.metrics.bbox_ioa(box1 (n, 4), box2 (m, 4), iou=False): intersection over the area of box2 -> (n, m).  Restated from the
+    published source (the package is a third-party dependency of the reference): parity unpinned by necessity."""
+    b1_x1, b1_y1, b1_x2, b1_y2 = box1.T
+    b2_x1, b2_y1, b2_x2, b2_y2 = box2.T
+    inter_area = (np.minimum(b1_x2[:, None], b2_x2) - np.maximum(b1_x1[:, None], b2_x1)).clip(0) * \
+                 (np.minimum(b1_y2[:, None], b2_y2) - np.maximum(b1_y1[:, None], b2_y1)).clip(0)
+    area = (b2_x2 - b2_x1) * (b2_y2 - b2_y1)
+    return inter_area / (area + eps)
+
+
+def _copy_paste(labels, segments, sample, w):
+    """The label half of copy_paste (augmentations.py:209-216) on the canvas of width w, in the reference's expressions and dtypes: for every
+    j of `sample` (the draw), the mirrored box against the labels AS GROWN SO FAR; where every ioa < 0.30, the mirrored label and polygon are
+    appended.  -> (labels, segments: what random_perspective sees; the accepted js, whose ORIGINAL polygons the image half fills)."""
+    if sample and max(sample) >= len(segments):
+        raise ValueError(f"copy_paste: the sample was drawn for more than the {len(segments)} polygons of this mosaic")
+    segments, accepted = list(segments), []
+    for j in sample:
+        label, segment = labels[j], segments[j]
+        box = w - label[3], label[2], w - label[1], label[4]
+        ioa = _bbox_ioa(np.array(box)[None], labels[:, 1:5])
+        if (ioa < 0.30).all():
+            labels = np.concatenate((labels, [[label[0], *box]]), 0)
+            segments.append(np.concatenate((w - segment[:, 0:1], segment[:, 1:2]), 1))
+            accepted.append(j)
+    return labels, segments, accepted
+
+
+def _canvas_stage(labels, segments, d, hw, pads, s):
+    """What load_mosaic hands to random_perspective (dataloaders.py:828-842; segment/dataloaders.py:266-280), or the letterbox branch of the
+    segmentation `__getitem__`: `_canvas_boxes`, the polygons likewise (xyn2xy in float32; mosaic only: clipped to the canvas), then
+    `_copy_paste` where the sample drew one.  -> (labels (n, 5), n polygons (k, 2) float32, the int32 polygons the image half pastes)."""
+    t, counts = _canvas_boxes(labels, d, hw, pads, s)
+    mosaic = d.get("mosaic", True)
+    segs = []
+    for i, (h, w), (padw, padh), k in zip(d["indices"], hw, pads, counts):
+        if len(segments[i]) != k:
+            raise ValueError(f"image {i}: {k} labels but {len(segments[i])} polygons")
+        if k:
+            # all polygons of the tile at once
+            y = _xyn2xy(np.concatenate([np.asarray(g, dtype=np.float32).reshape(-1, 2) for g in segments[i]], 0), w, h, padw, padh)
+            if mosaic:
+                np.clip(y, 0, 2 * s, out=y)
+            segs.extend(np.split(y, np.cumsum([len(g) for g in segments[i]])[:-1]))
+    paste = []
+    if mosaic and d.get("paste"):
+        t, segs, accepted = _copy_paste(t, segs, d["paste"], 2 * s)
+        paste = [segs[j].astype(np.int32) for j in accepted]               # augmentations.py:216
+    return t, segs, paste
+
+
+def _warp_polygons(t, segs, d, M, width, height):
+    """random_perspective's `use_segments` branch (augmentations.py:166-176, :193-195; all of segment/augmentations.py:71-89):
+    resample_segments(n = 1000), xy @ M.T, new box = segment2box(xy, width, height) (NOT the warped corners), box_candidates(area_thr = 0.01).
+    -> ((k, 5) [cls, x1, y1, x2, y2], (k, 1000, 2) float64 polygons) in output pixels."""
+    n = len(t)
+    if not n:
+        return t, np.zeros((0, 1000, 2))
+    xy = np.ones((n, 1000, 3))
+    xy[:, :, :2] = resample_segments(segs)
+    xy = (xy @ M.T)[:, :, :2]                                          # n products of the reference's own shape (1000, 3) @ (3, 3)
+    x, y = xy[:, :, 0], xy[:, :, 1]
+    ins = (x >= 0) & (y >= 0) & (x <= width) & (y <= height)            # segment2box (general.py:592-600)
+    any_in = ins.any(1)
+    new = np.stack((np.where(ins, x, np.inf).min(1), np.where(ins, y, np.inf).min(1), np.where(ins, x, -np.inf).max(1),
+                    np.where(ins, y, -np.inf).max(1)), 1)
+    new[~any_in] = 0.0
+    t, keep = _box_candidates(t, new, d["scale"], 0.01)
+    return t, xy[keep]
+
+
+def _labels(labels, segments, d, hw, pads, M, width, height, s):
+    """Label half of the sample up to random_perspective -> ((k, 5) [cls, x1, y1, x2, y2] in output pixels, the polygons to paste).
+    Without polygons, and on the letterbox branch (dataloaders.py:719-732 passes none): `_canvas_boxes`, corners through M + hull + clip +
+    box_candidates(area_thr = 0.10) (augmentations.py:177-195).  A mosaic of a dataset with polygons: `_canvas_stage` (copy_paste) and
+    the `use_segments` branch, `_warp_polygons`."""
+    paste = []
+    if segments is not None and d.get("mosaic", True):
+        t, segs, paste = _canvas_stage(labels, segments, d, hw, pads, s)
+        if any(x.any() for x in segs):                                   # use_segments (augmentations.py:164)
+            return _warp_polygons(t, segs, d, M, width, height)[0], paste
+    else:
+        t, _ = _canvas_boxes(labels, d, hw, pads, s)
     n = len(t)
     if n:
         pts = np.ones((n * 4, 3))
@@ -211,7 +307,7 @@ def _labels(labels, d, hw, pads, M, width, height, s):
         new[:, [0, 2]] = new[:, [0, 2]].clip(0, width)
         new[:, [1, 3]] = new[:, [1, 3]].clip(0, height)
         t, _ = _box_candidates(t, new, d["scale"], 0.10)
-    return t
+    return t, paste
 
 
 def _finish_labels(t, d, width, height):
@@ -285,36 +381,69 @@ def _finish_job(j, d, use_hsv):
     j.hsv, j.flipud, j.fliplr = int(use_hsv), int(bool(d["flipud"])), int(bool(d["fliplr"]))
 
 
-def _render(jobs, B, s, dev, dtype, normalize):
-    """The y5_mosaic_batch launch over a filled job table -> (B, 3, s, s)."""
+def paste_planes(polys, poly_plane, n_planes, S2, device):
+    """ONE y5_paste_planes launch (csrc/copy_paste.h): polys: int32 (k, 2) canvas polygons; poly_plane: their planes, ascending.
+    -> (n_planes, S2, ceil(S2 / 32)) int32 words; bit x & 31 of word x >> 5 of row y = the un-flipped union of the plane's filled polygons."""
+    plane = np.asarray(poly_plane, dtype=np.int32).reshape(-1)
+    if len(plane) != len(polys) or (len(plane) and (plane.min() < 0 or plane.max() >= n_planes or (np.diff(plane) < 0).any())):
+        raise ValueError("paste_planes: poly_plane must be ascending plane indices in [0, n_planes), one per polygon")
+    off = np.zeros(len(polys) + 1, dtype=np.int32)
+    np.cumsum([len(pg) for pg in polys], out=off[1:])
+    pts = [np.asarray(pg, dtype=np.int32).reshape(-1) for pg in polys]
+    meta = torch.from_numpy(np.concatenate((*pts, off, plane)).astype(np.int32)).to(device)
+    planes = torch.empty((n_planes, S2, (S2 + 31) // 32), dtype=torch.int32, device=device)
+    lib = _lib.lib()
+    p_off = meta.data_ptr() + 8 * int(off[-1])
+    _lib.check(lib.y5_paste_planes(C.c_void_p(meta.data_ptr()), C.c_void_p(p_off), C.c_void_p(p_off + 4 * len(off)), len(polys), n_planes, S2,
+                                   C.c_void_p(planes.data_ptr()), _lib.stream(device)), lib)
+    return planes
+
+
+def _render(jobs, B, s, dev, dtype, normalize, pasted=None):
+    """The y5_mosaic_batch launch over a filled job table -> (B, 3, s, s).  pasted: {job index: its int32 polygons to paste} in job-loop
+    order; when a job pastes, ONE `paste_planes` launch makes a plane per pasting job and the launch is y5_mosaic_batch_paste."""
     table = _lib.device_table(jobs, dev)
     out = torch.empty((B, 3, s, s), dtype=dtype, device=dev)
     lib = _lib.lib()
-    _lib.check(lib.y5_mosaic_batch(C.c_void_p(table.data_ptr()), B, s, 114, C.c_void_p(out.data_ptr()), _lib.dtype_code(dtype),
-                                   int(normalize and dtype != torch.uint8), _lib.stream(dev)), lib)
+    args = (B, s, 114, C.c_void_p(out.data_ptr()), _lib.dtype_code(dtype), int(normalize and dtype != torch.uint8), _lib.stream(dev))
+    if pasted:
+        job_plane = np.full(len(jobs), -1, dtype=np.int32)
+        for k, job in enumerate(pasted):
+            job_plane[job] = k
+        planes = paste_planes([pg for polys in pasted.values() for pg in polys], [k for k, polys in enumerate(pasted.values()) for _ in polys],
+                              len(pasted), 2 * s, dev)
+        job_plane = torch.from_numpy(job_plane).to(dev)
+        _lib.check(lib.y5_mosaic_batch_paste(C.c_void_p(table.data_ptr()), len(jobs), C.c_void_p(job_plane.data_ptr()),
+                                             C.c_void_p(planes.data_ptr()), *args), lib)
+    else:
+        _lib.check(lib.y5_mosaic_batch(C.c_void_p(table.data_ptr()), *args), lib)
     return out
 
 
 def _assemble(images, draws, s, hyp, sample_labels):
     """Host half of a training batch: the filled y5_mosaic_batch job table, the (k, 6) targets of every image and, when the dataset has them, the
-    warped polygons with their images.  sample_labels(d, hw, pads, M, width, height) -> (pixel boxes (k, 5),) or (pixel boxes, polygons (k, ...))
-    of one mosaic or letterboxed image.  -> (jobs, labs, polys, inst)."""
+    warped polygons with their images.  sample_labels(d, hw, pads, M, width, height) -> (pixel boxes (k, 5), paste) or (pixel boxes, polygons
+    (k, ...), paste) of one mosaic or letterboxed image, paste = the int32 canvas polygons copy_paste accepted (`_canvas_stage`).
+    -> (jobs, labs, polys, inst, pasted: {job index: paste} of the jobs that paste, the input of `_render`)."""
     B = len(draws)
     use_hsv = bool(hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"])
 
     def fill(j, d):
-        hw, pads, M, width, height = _fill_job(j, images, d, s)
-        return sample_labels(d, hw, pads, M, width, height), width, height
+        hw, pads, M, width, height = _fill_job(jobs[j], images, d, s)
+        *parts, paste = sample_labels(d, hw, pads, M, width, height)
+        if paste:
+            pasted[j] = paste
+        return parts, width, height
 
     jobs = (_lib.MosaicJob * (B + sum(d.get("partner") is not None for d in draws)))()
-    labs, polys, inst, npart = [], [], [], 0
+    labs, polys, inst, npart, pasted = [], [], [], 0, {}
     for b, d in enumerate(draws):
         j = jobs[b]
-        parts, width, height = fill(j, d)
+        parts, width, height = fill(b, d)
         if d.get("partner") is not None:
             # mixup (dataloaders.py:707-708; segment/augmentations.py:14-23): the partner mosaic is a job of its own behind the B rendered ones,
-            # its labels (and segments) are concatenated
-            parts2, _, _ = fill(jobs[B + npart], d["partner"])
+            # its labels (and segments) are concatenated; it ran its own copy_paste
+            parts2, _, _ = fill(B + npart, d["partner"])
             j.mix_job, j.mix_r = B + npart + 1, float(d["mix_r"])
             npart += 1
             parts = [np.concatenate(p, 0) for p in zip(parts, parts2)]
@@ -325,20 +454,22 @@ def _assemble(images, draws, s, hyp, sample_labels):
         for sg in parts[1:]:
             polys.extend(sg)
             inst.extend([b] * len(sg))
-    return jobs, labs, polys, inst
+    return jobs, labs, polys, inst, pasted
 
 
 def _targets(labs):
     return torch.from_numpy(np.concatenate(labs, 0) if labs else np.zeros((0, 6), np.float32))
 
 
-def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normalize=False):
+def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normalize=False, segments=None):
     """Render one training batch.  images: list of uint8 (h, w, 3) BGR tensors resident on the device (any sizes); labels: list of
-    (k, 5) arrays [cls, xc, yc, w, h] normalised; draws: list (one per output image) of `draw_sample` dicts.
+    (k, 5) arrays [cls, xc, yc, w, h] normalised; draws: list (one per output image) of `draw_sample` dicts.  segments: None, or per image
+    the list of (k, 2) normalised polygons of its label rows (a COCO-style label cache; ValueError when they are not one per row): the
+    mosaics then take random_perspective's `use_segments` branch, and the draws' copy_paste samples (`draw_sample(counts=...)`) are pasted.
     Returns (imgs (B, 3, s, s) `dtype` RGB CHW, targets (nt, 6) float32 [image index in batch, cls, xc, yc, w, h])."""
     hyp = HYP_AUG if hyp is None else hyp
-    jobs, labs, _, _ = _assemble(images, draws, s, hyp, lambda d, *geo: (_labels(labels, d, *geo, s),))
-    return _render(jobs, len(draws), s, images[0].device, dtype, normalize), _targets(labs)
+    jobs, labs, _, _, pasted = _assemble(images, draws, s, hyp, lambda d, *geo: _labels(labels, segments, d, *geo, s))
+    return _render(jobs, len(draws), s, images[0].device, dtype, normalize, pasted), _targets(labs)
 
 
 class MosaicLoader:
@@ -346,8 +477,13 @@ class MosaicLoader:
     shuffle=True / SmartDistributedSampler: rank r takes indices r::world of the epoch's permutation), each batch is one
     `mosaic_batch` launch.  Yields (imgs, targets, paths, shapes) like the reference's collate_fn."""
 
-    def __init__(self, images, labels, img_size=640, batch_size=16, hyp=None, dtype=torch.uint8, rank=-1, world_size=1, seed=0, paths=None):
+    def __init__(self, images, labels, img_size=640, batch_size=16, hyp=None, dtype=torch.uint8, rank=-1, world_size=1, seed=0, paths=None,
+                 segments=None):
+        if segments is not None and [len(sg) for sg in segments] != [len(lb) for lb in labels]:
+            raise ValueError("MosaicLoader: segments must hold one polygon per label row of every image")
         self.images, self.labels, self.s, self.bs = images, labels, img_size, batch_size
+        self.segments = segments                                          # see `mosaic_batch`
+        self.counts = None if segments is None else [len(sg) for sg in segments]
         self.hyp = dict(HYP_AUG if hyp is None else hyp)
         self.dtype, self.rank, self.world, self.seed, self.epoch = dtype, rank, world_size, seed, 0
         self.paths = paths or [f"image{i}" for i in range(len(images))]
@@ -383,8 +519,8 @@ class MosaicLoader:
         return order
 
     def _batch(self, ids):
-        draws = [draw_sample(i, len(self.images), self.s, self.hyp) for i in ids]
-        imgs, targets = mosaic_batch(self.images, self.labels, draws, self.s, self.hyp, self.dtype, normalize=True)
+        draws = [draw_sample(i, len(self.images), self.s, self.hyp, counts=self.counts) for i in ids]
+        imgs, targets = mosaic_batch(self.images, self.labels, draws, self.s, self.hyp, self.dtype, normalize=True, segments=self.segments)
         return imgs, targets, [self.paths[i] for i in ids], None
 
     def __iter__(self):
@@ -450,37 +586,11 @@ def _xyn2xy(x, w, h, padw, padh):
 
 
 def _seg_labels(labels, segments, d, hw, pads, M, width, height, s):
-    """Label half of one sample as utils/segment/augmentations.py:26-91 `random_perspective` computes it: `_canvas_boxes`, the polygons likewise
-    (xyn2xy in float32; mosaic only: clipped to the canvas, :276-277), resample_segments(n = 1000), xy @ M.T, new box =
-    segment2box(xy, width, height) (NOT the warped corners), box_candidates(area_thr = 0.01).
-    -> ((k, 5) float32 [cls, x1, y1, x2, y2], (k, 1000, 2) float64 polygons) in output pixels."""
-    t, counts = _canvas_boxes(labels, d, hw, pads, s)
-    segs, lens = [], []
-    for i, (h, w), (padw, padh), k in zip(d["indices"], hw, pads, counts):
-        if k:
-            if len(segments[i]) != k:
-                raise ValueError(f"image {i}: {k} labels but {len(segments[i])} polygons")
-            # all polygons of the tile at once
-            y = _xyn2xy(np.concatenate([np.asarray(g, dtype=np.float32).reshape(-1, 2) for g in segments[i]], 0), w, h, padw, padh)
-            if d.get("mosaic", True):
-                np.clip(y, 0, 2 * s, out=y)
-            segs.append(y)
-            lens.extend(len(g) for g in segments[i])
-    n = len(t)
-    if not n:
-        return t, np.zeros((0, 1000, 2))
-    pts = resample_segments(np.split(np.concatenate(segs, 0), np.cumsum(lens)[:-1]))
-    xy = np.ones((n, 1000, 3))
-    xy[:, :, :2] = pts
-    xy = (xy @ M.T)[:, :, :2]                                          # n products of the reference's own shape (1000, 3) @ (3, 3)
-    x, y = xy[:, :, 0], xy[:, :, 1]
-    ins = (x >= 0) & (y >= 0) & (x <= width) & (y <= height)            # segment2box (general.py:592-600)
-    any_in = ins.any(1)
-    new = np.stack((np.where(ins, x, np.inf).min(1), np.where(ins, y, np.inf).min(1), np.where(ins, x, -np.inf).max(1),
-                    np.where(ins, y, -np.inf).max(1)), 1)
-    new[~any_in] = 0.0
-    t, keep = _box_candidates(t, new, d["scale"], 0.01)
-    return t, xy[keep]
+    """Label half of one sample as the segmentation loader computes it: `_canvas_stage`, then utils/segment/augmentations.py:26-91
+    `random_perspective`, `_warp_polygons`.  -> ((k, 5) float32 [cls, x1, y1, x2, y2], (k, 1000, 2) float64 polygons in output pixels,
+    the polygons to paste)."""
+    t, segs, paste = _canvas_stage(labels, segments, d, hw, pads, s)
+    return (*_warp_polygons(t, segs, d, M, width, height), paste)
 
 
 def polygon_masks(polys, inst_img, B, H, W, ratio, overlap, flips, device):
@@ -535,6 +645,10 @@ def _reorder(labs, order):
 def seg_mosaic_geometry(images, labels, segments, draws, s, hyp):
     """Host half of `seg_mosaic_batch`: the filled y5_mosaic_batch job table, the (k, 6) targets of every image in LABEL order, and the warped
     polygons (float64 output pixels) with their images -- the input of `polygon_masks`."""
+    return _seg_assemble(images, labels, segments, draws, s, hyp)[:4]
+
+
+def _seg_assemble(images, labels, segments, draws, s, hyp):
     return _assemble(images, draws, s, hyp, lambda d, *geo: _seg_labels(labels, segments, d, *geo, s))
 
 
@@ -554,8 +668,8 @@ def seg_mosaic_batch(images, labels, segments, draws, s, hyp=None, dtype=torch.u
     hyp = HYP_AUG if hyp is None else hyp
     dev = images[0].device
     B = len(draws)
-    jobs, labs, polys, inst = seg_mosaic_geometry(images, labels, segments, draws, s, hyp)
-    out = _render(jobs, B, s, dev, dtype, normalize)
+    jobs, labs, polys, inst, pasted = _seg_assemble(images, labels, segments, draws, s, hyp)
+    out = _render(jobs, B, s, dev, dtype, normalize, pasted)
     flips = [(bool(d["flipud"]), bool(d["fliplr"])) for d in draws]
     targets, masks = _masks_and_targets(labs, polys, inst, B, s, mask_ratio, overlap, flips, dev)
     return out, targets, masks
@@ -564,17 +678,20 @@ def seg_mosaic_batch(images, labels, segments, draws, s, hyp=None, dtype=torch.u
 class SegMosaicLoader(MosaicLoader):
     """`MosaicLoader` for a segmentation dataset (utils/segment/dataloaders.py `LoadImagesAndLabelsAndMasks`, augment = True, rect = False):
     yields (imgs, targets, paths, None, masks) as the reference's collate_fn does -- the batch `segment_loss.ComputeLoss` and
-    `train_loop.train` take.  labels may be None: they are then derived from the polygons (`labels_from_segments` needs `classes`)."""
+    `train_loop.train` take.  labels may be None: they are then derived from the polygons (`labels_from_segments` needs `classes`).
+    hyp['copy_paste'] > 0 (data/hyps/hyp.scratch-high.yaml: 0.1) pastes mirrored instances into the mosaics as utils/augmentations.py:200-222 does:
+    the pasted polygons become label rows and go through the same warp into the one `y5_polygon_masks` call; per batch the order is host
+    geometry, one y5_paste_planes launch (skipped when no job pasted), the render launch, the mask call -- no further device-to-host read."""
 
     def __init__(self, images, labels, segments, img_size=640, batch_size=16, hyp=None, dtype=torch.uint8, rank=-1, world_size=1, seed=0,
                  paths=None, overlap=True, mask_ratio=4, classes=None):
         if labels is None:
             labels = [labels_from_segments(c, sg) for c, sg in zip(classes, segments)]
-        super().__init__(images, labels, img_size, batch_size, hyp, dtype, rank, world_size, seed, paths)
-        self.segments, self.overlap, self.mask_ratio = segments, overlap, mask_ratio
+        super().__init__(images, labels, img_size, batch_size, hyp, dtype, rank, world_size, seed, paths, segments)
+        self.overlap, self.mask_ratio = overlap, mask_ratio
 
     def _batch(self, ids):
-        draws = [draw_sample_seg(i, len(self.images), self.s, self.hyp) for i in ids]
+        draws = [draw_sample_seg(i, len(self.images), self.s, self.hyp, counts=self.counts) for i in ids]
         imgs, targets, masks = seg_mosaic_batch(self.images, self.labels, self.segments, draws, self.s, self.hyp, self.dtype, normalize=True,
                                                 overlap=self.overlap, mask_ratio=self.mask_ratio)
         return imgs, targets, [self.paths[i] for i in ids], None, masks
