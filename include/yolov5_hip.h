@@ -726,6 +726,17 @@ int y5_mosaic_batch_paste(const y5_mosaic_job* jobs_dev, int n_jobs, const int* 
                           void* dst, int dst_dtype, int div255, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * y5_collate4 -- the image half of `LoadImagesAndLabels.collate_fn4` (utils/dataloaders.py:865-891; train.py --quad) for a whole batch in
+ * one launch.  src: (B, C, H, W) uint8, B >= 4; flags_dev: DEVICE array of n = B / 4 bytes, the host's `random.random() < 0.5` per output
+ * image (:877); dst: (n, C, 2H, 2W) uint8.  flag 1: the 2x bilinear upsample (align_corners = False) of image 4i, computed in fp32 on the byte
+ * values and truncated to uint8 (:878-880); flag 0: images 4i over 4i + 1 in the left column, 4i + 2 over 4i + 3 in the right column (:883).
+ * The B % 4 trailing images are not read (:869).  Any H, W >= 1; 16 bytes per lane when W % 16 == 0 and both tensors are 16-byte aligned.
+ * Every output byte equals torch's CPU result (the weights are multiples of 1/4: the fp32 arithmetic is exact).  The labels are the host's
+ * (yolov5_amd/dataloaders.py `collate_fn4`).  Kernel: csrc/collate4.h.
+ * ------------------------------------------------------------------------------------------------------- */
+int y5_collate4(const unsigned char* src, int B, int C, int H, int W, const unsigned char* flags_dev, unsigned char* dst, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * y5_polygon_masks -- the mask half of the segmentation input pipeline for a whole batch: utils/segment/dataloaders.py:180-199
  * (`polygons2masks_overlap` / `polygons2masks` of ultralytics.data.utils, i.e. per instance np.asarray(polygon, int32) ->
  * cv2.fillPoly(zeros(H, W), [pts], 1) -> cv2.resize to (H / ratio, W / ratio)), the mask flips of :212-223 and collate_fn's

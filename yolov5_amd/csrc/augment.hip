@@ -23,6 +23,7 @@
 #include "resize_u8.h"
 #include "seg_data.h"   // y5_polygon_masks: the mask half of the segmentation input pipeline
 #include "copy_paste.h" // y5_paste_planes: the bit planes of the copy-paste augmentation (utils/augmentations.py:200-222)
+#include "collate4.h"   // y5_collate4: the image half of collate_fn4 (utils/dataloaders.py:865-891, train.py --quad)
 
 namespace {
 struct AugParams {

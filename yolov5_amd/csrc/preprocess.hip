@@ -165,7 +165,10 @@ void y5_scale_img_kernel(const ScaleParams p) {
   const int oy = (int)(id / p.PW), ox = (int)(id - (long long)oy * p.PW);
   float v = p.pad;
   if (oy < p.OH && ox < p.OW) {
-    float fy = p.sh * ((float)oy + 0.5f) - 0.5f, fx = p.sw * ((float)ox + 0.5f) - 0.5f;   // area_pixel_compute_source_index, align_corners = False
+    // area_pixel_compute_source_index, align_corners = False.  ONE rounding (an explicit fma; the file is built with contraction off), as torch's
+    // CPU and GPU kernels evaluate `scale * (dst + 0.5) - 0.5`: with a scale that is no power of two (96 -> 160) the two-rounding form lands one
+    // ulp of the index beside torch's, which a 0 / 1 edge turns into 32 * 2^-24 of the pixel (multi-scale's pixel bound is 8 * 2^-24)
+    float fy = fmaf(p.sh, (float)oy + 0.5f, -0.5f), fx = fmaf(p.sw, (float)ox + 0.5f, -0.5f);
     fy = fy < 0.f ? 0.f : fy;
     fx = fx < 0.f ? 0.f : fx;
     const int y0 = (int)fy, x0 = (int)fx;

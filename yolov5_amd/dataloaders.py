@@ -472,15 +472,58 @@ def mosaic_batch(images, labels, draws, s, hyp=None, dtype=torch.uint8, normaliz
     return _render(jobs, len(draws), s, images[0].device, dtype, normalize, pasted), _targets(labs)
 
 
+def collate_fn4(imgs, targets, paths, shapes, rng=random):
+    """`LoadImagesAndLabels.collate_fn4` (utils/dataloaders.py:865-891; train.py --quad) on a batch that `collate_fn` already made: imgs
+    (B, C, H, W) uint8 on the device, targets (nt, 6) float32 with the image index in column 0.  Every group of four images becomes one
+    (C, 2H, 2W) image -- by a coin per group (`rng.random() < 0.5`, drawn in order AFTER every sample draw of the batch, as the reference's
+    collate runs after its __getitem__s) the 2x bilinear upsample of the first with its labels, or the 2 x 2 tiling of the four with the
+    labels shifted and halved by the reference's own expression in float32.  One `y5_collate4` launch (csrc/collate4.h) makes the images.
+    -> (imgs (B // 4, C, 2H, 2W) uint8, targets, paths[:B // 4], shapes[:B // 4]); the B % 4 trailing samples are dropped (:869)."""
+    if imgs.dtype != torch.uint8:
+        raise TypeError("collate_fn4: a uint8 image batch is expected (the reference's loader collates uint8 images)")
+    if imgs.dim() != 4 or not _lib.accepts(imgs):
+        raise TypeError("collate_fn4: a (B, C, H, W) GPU batch is expected")
+    B, Cn, H, W = (int(v) for v in imgs.shape)
+    n = B // 4
+    if n < 1:
+        raise ValueError(f"collate_fn4: a quad batch needs at least 4 samples, got {B}")
+    flags = [rng.random() < 0.5 for _ in range(n)]                                                   # :877
+    imgs = imgs.contiguous()
+    dev = imgs.device
+    out = torch.empty((n, Cn, 2 * H, 2 * W), dtype=torch.uint8, device=dev)
+    fl = torch.tensor(flags, dtype=torch.uint8).to(dev)
+    lib = _lib.lib()
+    _lib.check(lib.y5_collate4(C.c_void_p(imgs.data_ptr()), B, Cn, H, W, C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), _lib.stream(dev)), lib)
+    t = targets.detach().cpu().float()
+    label = [t[t[:, 0] == b] for b in range(4 * n)]          # (boolean selection keeps the row order and copies)
+    ho = torch.tensor([[0.0, 0, 0, 1, 0, 0]])
+    wo = torch.tensor([[0.0, 0, 1, 0, 0, 0]])
+    s = torch.tensor([[1, 1, 0.5, 0.5, 0.5, 0.5]])
+    label4 = []
+    for i, up in enumerate(flags):
+        a, b, c, d = label[4 * i:4 * i + 4]
+        lb = a if up else torch.cat((a, b + ho, c + wo, d + ho + wo), 0) * s                            # :881, :884
+        lb[:, 0] = i                                                                                   # :888-889
+        label4.append(lb)
+    return out, torch.cat(label4, 0), paths[:n] if paths is not None else None, shapes[:n] if shapes is not None else None
+
+
 class MosaicLoader:
     """Re-iterable training loader over an in-HBM dataset: every epoch visits the images in a fresh random order (DataLoader
     shuffle=True / SmartDistributedSampler: rank r takes indices r::world of the epoch's permutation), each batch is one
-    `mosaic_batch` launch.  Yields (imgs, targets, paths, shapes) like the reference's collate_fn."""
+    `mosaic_batch` launch.  Yields (imgs, targets, paths, shapes) like the reference's collate_fn.
+    quad=True (train.py --quad, utils/dataloaders.py:159,184): every batch goes through `collate_fn4` -- batch_size / 4 images of twice the
+    side -- and the trailing incomplete batch of an epoch is dropped (`drop_last=quad`); the images must be uint8."""
 
     def __init__(self, images, labels, img_size=640, batch_size=16, hyp=None, dtype=torch.uint8, rank=-1, world_size=1, seed=0, paths=None,
-                 segments=None):
+                 segments=None, quad=False):
         if segments is not None and [len(sg) for sg in segments] != [len(lb) for lb in labels]:
             raise ValueError("MosaicLoader: segments must hold one polygon per label row of every image")
+        if quad and dtype != torch.uint8:
+            raise TypeError("MosaicLoader: quad batches are collated from uint8 images (collate_fn4)")
+        if quad and batch_size < 4:
+            raise ValueError("MosaicLoader: quad needs batch_size >= 4")
+        self.quad = bool(quad)
         self.images, self.labels, self.s, self.bs = images, labels, img_size, batch_size
         self.segments = segments                                          # see `mosaic_batch`
         self.counts = None if segments is None else [len(sg) for sg in segments]
@@ -505,7 +548,7 @@ class MosaicLoader:
         return np.array([[int(im.shape[1]), int(im.shape[0])] for im in self.images], dtype=np.float64)
 
     def __len__(self):
-        return (self.n_local + self.bs - 1) // self.bs
+        return self.n_local // self.bs if self.quad else (self.n_local + self.bs - 1) // self.bs
 
     def _epoch_order(self):
         """This rank's image ids of the current epoch: the seeded shuffle, every `world`-th from `rank`, padded to the common length."""
@@ -525,8 +568,9 @@ class MosaicLoader:
 
     def __iter__(self):
         order = self._epoch_order()
-        for b0 in range(0, len(order), self.bs):
-            yield self._batch(order[b0:b0 + self.bs])
+        for b0 in range(0, len(self) * self.bs if self.quad else len(order), self.bs):
+            batch = self._batch(order[b0:b0 + self.bs])
+            yield collate_fn4(*batch) if self.quad else batch
         self.epoch += 1
 
 
@@ -684,7 +728,10 @@ class SegMosaicLoader(MosaicLoader):
     geometry, one y5_paste_planes launch (skipped when no job pasted), the render launch, the mask call -- no further device-to-host read."""
 
     def __init__(self, images, labels, segments, img_size=640, batch_size=16, hyp=None, dtype=torch.uint8, rank=-1, world_size=1, seed=0,
-                 paths=None, overlap=True, mask_ratio=4, classes=None):
+                 paths=None, overlap=True, mask_ratio=4, classes=None, quad=False):
+        if quad:
+            # the reference's LoadImagesAndLabelsAndMasks inherits collate_fn4, which cannot unpack its 5-tuples (utils/segment/dataloaders.py:82)
+            raise NotImplementedError("SegMosaicLoader: quad batches are not defined for the segmentation loader")
         if labels is None:
             labels = [labels_from_segments(c, sg) for c, sg in zip(classes, segments)]
         super().__init__(images, labels, img_size, batch_size, hyp, dtype, rank, world_size, seed, paths, segments)

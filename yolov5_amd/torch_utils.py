@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import random
 from contextlib import contextmanager
 from copy import deepcopy
 
@@ -69,7 +70,7 @@ class HipDDP(nn.Module):
         # RCCL kernel (rocprofv3: 0 nccl dispatches), so its "exposed exchange" never was CU starvation.  What it is: see _launch.  The knob stays for
         # N > 1, where RCCL's ring kernels do need workgroup slots beside the plan's persistent workgroups.
         self.reserve_cus = int(os.environ.get("Y5_DDP_RESERVE_CUS", "0")) if self.avg_in_collective else 0
-        self.buckets, self.p2b, self._eng, self._flat = [], {}, None, None
+        self.buckets, self.p2b, self._eng, self._flat, self._arena = [], {}, None, None, None
         module.__dict__["_ddp_sink"] = self
         for k in ("stride", "names", "hyp", "nc", "yaml"):
             if hasattr(module, k):
@@ -80,7 +81,7 @@ class HipDDP(nn.Module):
 
     def _attach(self, eng):
         """Cut the engine's arena (gradients in production order) into buckets of at most `cap` floats."""
-        self._eng = eng
+        self._eng, self._arena = eng, eng.gflat
         self._flat = eng.be.view_torch(eng.gflat)
         order = sorted(eng.goff, key=eng.goff.get)
         self.buckets, cur, lo = [], [], 0
@@ -97,8 +98,11 @@ class HipDDP(nn.Module):
 
     # ---- gradient sink protocol (called by TrainEngine.backward) -------------------------------------------------------
     def begin(self, eng):
-        if eng is not self._eng:
+        # keyed on the gradient ARENA, not on the engine: the plans of a model's training-plan cache (train_engine.set_plan_cache) share one
+        # arena, so a switch between cached input shapes keeps the buckets; a plan with an arena of its own re-cuts them
+        if eng.gflat is not self._arena:
             self._attach(eng)
+        self._eng = eng
         if self.reserve_cus > 0:
             _state.set_cu_budget(eng.lib, self._ncu(eng) - self.reserve_cus)
         for b in self.buckets:
@@ -184,6 +188,32 @@ def scale_img(img, ratio=1.0, same_shape=False, gs=32, flip=None):
     lib = _lib.lib()
     _lib.check(lib.y5_scale_img(C.c_void_p(img.data_ptr()), code, B, Cn, h, w, int(flip or 0), s[0], s[1], ph, pw, 0.447,
                                 C.c_void_p(out.data_ptr()), code, _lib.stream(img.device)), lib)
+    return out
+
+
+def multi_scale(imgs, imgsz, gs, dtype, rng=random):
+    """train.py:392-398 (`--multi-scale`; segment/train.py:370-376): ONE draw of the batch's size per call -- a multiple of `gs` out of
+    [int(imgsz * 0.5), int(imgsz * 1.5) + gs), floored to the grid (the lower end itself is no multiple of gs for most imgsz: imgsz = 640 draws
+    from 320 .. 960, 21 sizes; with an imgsz whose half is no multiple of gs the lowest size is rarer than the rest) -- the scale factor against the batch's longer side, and both sides stretched
+    to the next multiple of gs.  sf == 1: `imgs` itself, nothing launched.  Otherwise F.interpolate(size=ns, mode="bilinear", align_corners=False)
+    as one `y5_scale_img` launch (no flip, no padding) that writes `dtype` (float16 for the AMP plan, float32 for the fp32 plan): uint8 batches are
+    read as x / 255 and float32 batches as they are, interpolated in fp32 and rounded once on the store, like the reference's fp32 interpolation
+    with autocast's rounding behind it."""
+    if imgs.dim() != 4 or imgs.dtype not in (torch.uint8, torch.float16, torch.float32) or not _lib.accepts(imgs):
+        raise TypeError("multi_scale: a uint8 / float16 / float32 NCHW GPU batch is expected")
+    if dtype not in (torch.float16, torch.float32):
+        raise TypeError("multi_scale: the output dtype must be float16 or float32")
+    B, Cn, h, w = (int(v) for v in imgs.shape)
+    sz = rng.randrange(int(imgsz * 0.5), int(imgsz * 1.5) + gs) // gs * gs
+    sf = sz / max(h, w)
+    if sf == 1:
+        return imgs
+    ns = [math.ceil(x * sf / gs) * gs for x in (h, w)]
+    imgs = imgs.contiguous()
+    out = torch.empty((B, Cn, ns[0], ns[1]), dtype=dtype, device=imgs.device)
+    lib = _lib.lib()
+    _lib.check(lib.y5_scale_img(C.c_void_p(imgs.data_ptr()), _lib.dtype_code(imgs.dtype), B, Cn, h, w, 0, ns[0], ns[1], ns[0], ns[1], 0.0,
+                                C.c_void_p(out.data_ptr()), _lib.dtype_code(dtype), _lib.stream(imgs.device)), lib)
     return out
 
 

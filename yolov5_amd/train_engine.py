@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import OrderedDict
 
 import torch
 
@@ -51,8 +52,10 @@ def _vp(v):
 class TrainEngine:
     """Materialised training plan for one (batch, resolution) on one GPU."""
 
-    def __init__(self, model, x_shape, device, backend=None, dtype=torch.float16):
-        """dtype: torch.float16 = AMP semantics (fp16 activations / gradients, fp32 master weights and accumulators: the production
+    def __init__(self, model, x_shape, device, backend=None, dtype=torch.float16, arena=None):
+        """arena: None = the plan allocates its own gradient arena; a `_GradArena` = the arena the plans of one model share (the training-plan
+        cache, `train_forward`): allocated by the first plan built with it, received by the later ones.
+        dtype: torch.float16 = AMP semantics (fp16 activations / gradients, fp32 master weights and accumulators: the production
         path); torch.float32 = the whole step in fp32 (exact-fp32 MFMA forward / data gradient, plain fp32 weight gradient): the
         reference-precision mode the end-to-end gradient check against the oracle's autograd runs in."""
         if dtype not in (torch.float16, torch.float32):
@@ -80,13 +83,22 @@ class TrainEngine:
         # order): kernels write parameter gradients straight into it, HipDDP all-reduces contiguous ranges of it, the fused
         # optimizer reads it -- no per-parameter copies.  Slots are padded to 64 floats (Detect's 255-channel bias
         # gradient is produced 256 wide).
-        self.goff, off = {}, 0
-        for i in reversed(range(len(self.params))):
-            self.goff[i] = off
-            off += round_up(self.params[i].numel(), 64)
-        self.gtotal = off
-        self.gflat = self.be.empty((max(off, 64),), torch.float32)
-        self.be.zero_(self.gflat)
+        # The layout depends on the parameter list alone, not on the input shape: the plans of a training-plan cache share ONE arena, so .grad
+        # keeps its address across shapes (the optimizer's device table and HipDDP's buckets survive a switch).
+        self._closed = False
+        self._owns_arena = arena is None or arena.gflat is None
+        if self._owns_arena:
+            self.goff, off = {}, 0
+            for i in reversed(range(len(self.params))):
+                self.goff[i] = off
+                off += round_up(self.params[i].numel(), 64)
+            self.gtotal = off
+            self.gflat = self.be.empty((max(off, 64),), torch.float32)
+            self.be.zero_(self.gflat)
+            if arena is not None:
+                arena.gflat, arena.goff, arena.gtotal = self.gflat, self.goff, self.gtotal
+        else:
+            self.gflat, self.goff, self.gtotal = arena.gflat, arena.goff, arena.gtotal
         self.raw = {}
         self.seg = False
         self.proto = None
@@ -149,6 +161,44 @@ class TrainEngine:
             ncu = max(256, torch.cuda.get_device_properties(self.be.device).multi_processor_count)
         self.stats_ws_bytes = ncu * 8 * 2 * 256 * 4   # one [2][<= 256 channels] fp32 row per workgroup, <= 8 workgroups per CU
         self.stats_ws = self.be.empty((self.stats_ws_bytes,), torch.uint8) if self.fused_stats else None
+
+    # ---- size and release ---------------------------------------------------------------------------------------------
+    def _buffers(self):
+        """Every device buffer this plan owns (the shared gradient arena counts for the plan that allocated it; the head maps, proto and logits
+        of a forward are the caller's)."""
+        out = list(self.bufs) + list(self.gbufs) + [self.dz, self.dwflat, self.ws, self.stats_ws, self._wg_ws]
+        if self._owns_arena:
+            out.append(self.gflat)
+        for st in self.convs:
+            out += [st.get(k) for k in ("z", "mean", "invstd", "dbias", "wp", "bp", "stem_w", "zb", "sums", "gsum")]
+            out += [sub["w"] for sub in st.get("subs", ())]
+        if self.cls is not None:
+            out += [self.cls["pooled"], self.cls["ws"], self.cls["w16"]]
+        out += [ent[1] for ent in self.__dict__.get("_job_tables", {}).values()]
+        return [b for b in out if b is not None]
+
+    @property
+    def nbytes(self):
+        """Bytes of device memory the plan holds: what the training-plan cache's byte budget adds up."""
+        return sum(int(b.nbytes) for b in self._buffers())
+
+    def close(self):
+        """Release the plan's device buffers NOW (eviction from the training-plan cache).  The per-convolution states and the plan's ops refer to
+        each other (st["op"] / op["_st"]), so dropping the engine would leave the buffers to the cycle collector: the references are cut here.
+        A closed plan refuses forward and backward."""
+        self._closed = True
+        for st in self.convs:
+            st["op"].pop("_st", None)
+            st.clear()
+        self.convs, self.bufs, self.gbufs = [], [], []
+        self.dz = self.dwflat = self.ws = self.stats_ws = self._wg_ws = None
+        self.cls, self.raw, self.proto, self.logits = None, {}, None, None
+        self._keep, self._nbt = [], []
+        self.__dict__.pop("_job_tables", None)
+        self.__dict__.pop("_run_tmp", None)
+        self.gflat = None     # (the arena itself lives on with the plans -- and the .grad views -- that still use it)
+        self._owns_arena = False
+        self.grad_sink = self.debug_hook = None
 
     # ---- helpers ---------------------------------------------------------------------------------------------------
     def _ptr(self, t: TRef, grad=False):
@@ -311,6 +361,8 @@ class TrainEngine:
     # ---- forward ---------------------------------------------------------------------------------------------------
     def forward(self, x):
         lib, be, B = self.lib, self.be, self.spec.B
+        if self._closed:
+            raise RuntimeError("yolov5_amd: this training plan was evicted from the model's plan cache and released its buffers")
         if tuple(x.shape) != self.x_shape:
             raise ValueError(f"training engine built for input {self.x_shape}, got {tuple(x.shape)}")
         stm = be.stream()
@@ -801,13 +853,16 @@ class _TrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dps):
         eng = ctx.eng
-        if ctx.seq != eng._fwd_seq:
+        if eng._closed or ctx.seq != eng._fwd_seq:
             # activations, BatchNorm statistics and the raw head maps live in engine-owned buffers that the later forward overwrote
             # (the reference would keep one autograd graph per forward alive; one training plan holds exactly one)
+            # (with a training-plan cache: the latest one AT THIS SHAPE, and the plan must not have been evicted since)
             raise RuntimeError("yolov5_amd: backward() of a training forward that is no longer the model's latest one -- "
                                "call backward before the next train-mode forward at this input shape")
         # gradient accumulation (a second backward before zero_grad): .grad tensors that alias the arena would be overwritten
-        # by this pass before autograd adds to them -- give those their own storage first, and hand autograd copies
+        # by this pass before autograd adds to them -- give those their own storage first, and hand autograd copies.  The plans of a
+        # plan cache share the arena, so this also holds when the earlier backward belonged to ANOTHER shape's plan (accumulate > 1 under
+        # multi-scale): its .grad views lie inside [lo, hi) of this plan's arena all the same.
         lo = eng.be.ptr(eng.gflat)
         hi = lo + eng.gtotal * 4
         accumulating = False
@@ -822,20 +877,104 @@ class _TrainFn(torch.autograd.Function):
         return (None, None, *grads)
 
 
+class _GradArena:
+    """The gradient arena the plans of one model share: allocated by the first plan built with it (TrainEngine.__init__)."""
+
+    def __init__(self, key):
+        self.key, self.gflat, self.goff, self.gtotal = key, None, None, 0
+
+
+PLAN_KEYS = ("_train_max_plans", "_train_max_bytes")   # model.__dict__ keys of the limits (BaseModel.__getstate__ pops them)
+
+
+def set_plan_cache(model, max_plans=None, max_bytes=None):
+    """Limits of the model's cache of training plans (`train_forward` keeps an LRU of TrainEngines keyed by (input shape, device, dtype)).
+    max_plans: how many plans may be live; None = the environment's Y5_TRAIN_PLAN_CACHE, default 1 -- one plan, a new shape drops it and builds
+    a fresh one that owns its gradient arena.  With more than one, the plans share one arena (see TrainEngine.__init__).
+    max_bytes: budget over the sum of the plans' `nbytes`; None = half of the device's total memory (torch.cuda.mem_get_info).  A policy, not a
+    measurement of what is free: a plan that alone exceeds it is still built and kept as the only one.
+    Plans over the new limits are evicted at once, least recently used first.  Returns the previous (max_plans, max_bytes) as they were set."""
+    prev = tuple(model.__dict__.get(k) for k in PLAN_KEYS)
+    for k, v in zip(PLAN_KEYS, (max_plans, max_bytes)):
+        if v is None:
+            model.__dict__.pop(k, None)
+        else:
+            model.__dict__[k] = int(v)
+    cache = model.__dict__.get("_train_engines")
+    if cache:
+        mp, mb = _limits(model, next(iter(cache.values())))
+        _evict(model, cache, mp, mb)
+    return prev
+
+
+def _limits(model, eng=None, device=None):
+    """(max_plans, max_bytes) in force for `model`; the byte budget is looked up only where more than one plan may live."""
+    mp = model.__dict__.get(PLAN_KEYS[0])
+    if mp is None:
+        mp = int(os.environ.get("Y5_TRAIN_PLAN_CACHE", "1"))
+    mp = max(1, int(mp))
+    mb = model.__dict__.get(PLAN_KEYS[1])
+    if mb is None and mp > 1:
+        dev = device if device is not None else getattr(eng.be, "device", None)
+        if dev is not None and torch.device(dev).type == "cuda":
+            mb = torch.cuda.mem_get_info(dev)[1] // 2
+    return mp, mb
+
+
+def _evict(model, cache, max_plans, max_bytes, room=0):
+    """Drop least recently used plans until at most max_plans - room are left and (while more than one is left) their bytes fit the budget."""
+    def over():
+        if len(cache) > max(max_plans - room, 0):
+            return True
+        return max_bytes is not None and len(cache) > 1 and sum(e.nbytes for e in cache.values()) > max_bytes
+
+    while cache and over():
+        _, old = cache.popitem(last=False)
+        old.close()
+    if max_plans == 1:
+        model.__dict__.pop("_train_arena", None)   # a single plan owns its arena, as before there was a cache
+
+
 def train_forward(model, x):
     """Train-mode `BaseModel._forward_once` (models/yolo.py:160-170): list of (bs, na, ny, nx, no) tensors; for a Segment head
     (p, proto) with proto (bs, nm, mh, mw) (models/yolo.py:150); for a Classify head the (bs, nc) logits tensor."""
     # fp32 images -> the fp32 plan (reference-precision mode: train.py without AMP); fp16 / uint8 images -> the fp16 (AMP) plan
     dtype = torch.float32 if x.dtype == torch.float32 else torch.float16
     key = (tuple(x.shape), str(x.device), dtype)
-    cache = model.__dict__.setdefault("_train_engines", {})
+    cache = model.__dict__.get("_train_engines")
+    if cache is None:
+        cache = model.__dict__["_train_engines"] = OrderedDict()
     eng = cache.get(key)
     if eng is None:
-        cache.clear()
-        eng = TrainEngine(model, tuple(x.shape), x.device, dtype=dtype)
+        # A bounded LRU of plans per model (set_plan_cache).  The default of ONE plan is the behaviour from before the cache: the old plan goes
+        # first, the new one owns its arena.  With more, the plans share the gradient arena; the count is made to fit BEFORE the build (no more
+        # than max_plans ever live), the byte budget after its first forward (a plan's size is known once it stands and has run).
+        mp, mb = _limits(model, device=x.device)
+        arena = None
+        if mp == 1:
+            cache.clear()   # (not closed: a forward of the dropped plan that is still waiting for its backward keeps working, as it always did)
+            model.__dict__.pop("_train_arena", None)
+        else:
+            akey = (tuple(id(p) for p in model.parameters()), str(x.device))
+            arena = model.__dict__.get("_train_arena")
+            if arena is None or arena.key != akey:
+                arena = model.__dict__["_train_arena"] = _GradArena(akey)
+                only = next(iter(cache.values())) if len(cache) == 1 else None
+                if only is not None and only._owns_arena and tuple(id(p) for p in only.params) == akey[0] and next(iter(cache))[1] == akey[1]:
+                    arena.gflat, arena.goff, arena.gtotal = only.gflat, only.goff, only.gtotal   # the single plan from before: its arena is adopted
+                else:
+                    _evict(model, cache, 0, None)   # (the parameters were replaced: plans on another arena go)
+            _evict(model, cache, mp, None, room=1)
+        eng = TrainEngine(model, tuple(x.shape), x.device, dtype=dtype, arena=arena)
         cache[key] = eng
+        fresh = True
+    else:
+        cache.move_to_end(key)
+        fresh = False
     eng.grad_sink = model.__dict__.get("_ddp_sink")
     outs = list(_TrainFn.apply(eng, x, *eng.params))
+    if fresh:
+        _evict(model, cache, mp, mb)   # (behind the plan's first forward: its job tables are allocated there and count)
     if eng.cls is not None:
         return outs[0]  # ClassificationModel: the (bs, nc) logits (models/common.py:1140)
     return (outs[:-1], outs[-1]) if eng.seg else outs  # Segment: (p, proto) (models/yolo.py:150)

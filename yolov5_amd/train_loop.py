@@ -17,6 +17,7 @@ flag with a non-blocking copy one iteration later to adjust the scale (no pipeli
 from __future__ import annotations
 
 import math
+import sys
 
 from copy import deepcopy
 
@@ -106,7 +107,7 @@ def host_amp_step(optimizer, parameters, scaler, max_norm=10.0):
 
 def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_lr=False, amp=True, ema=True, world_size=1, rank=-1,
           optimizer_name="SGD", max_norm=10.0, start_epoch=0, on_batch_end=None, nbs=64, val_loader=None, noval=False, sync_bn=False,
-          overlap=True, autoanchor=None, imgsz=None, fused_optimizer=False):
+          overlap=True, autoanchor=None, imgsz=None, fused_optimizer=False, multi_scale=False, gs=None, quad=False):
     """Runs `epochs` epochs over `loader` (iterable of (imgs uint8|float BCHW, targets (nt, 6), *rest), re-iterable, len() = batches
     per epoch).  Returns dict(model, ema, optimizer, scheduler, scaler, mloss per epoch, losses per iteration, lr per epoch).
     rank / world_size as train.py's RANK / WORLD_SIZE (-1 / 1: single process; otherwise torch.distributed is initialised and the
@@ -120,7 +121,30 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
     `--noautoanchor` is given, here it runs only when asked for -- with None nothing changes and no RNG is consumed.  The result
     (bpr, aat, replaced) is returned under "autoanchor".
     fused_optimizer: smart_optimizer(fused=True) -- "Adam" / "AdamW" / "RMSProp" take the device path of "SGD" (step_fused) instead of host_amp_step.
-    Off by default, as the reference's optimizers are."""
+    Off by default, as the reference's optimizers are.
+    multi_scale: train.py:392-398 `--multi-scale` (segment/train.py:370-376 alike; only the images are resized, the segmentation loss resamples
+    the masks to the proto size itself): once per batch, behind the warm-up block and before the forward, on every rank and on warm-up
+    iterations too, `torch_utils.multi_scale` draws a size around `imgsz` (the loader's `s`, else 640) on the grid `gs` (default
+    max(int(model.stride.max()), 32), train.py:219) from Python's `random` and resizes the batch in one launch.  For the run the model's
+    training-plan cache is unbounded in count (`train_engine.set_plan_cache`; the byte budget stays the default): every size keeps its plan, all
+    of them on one gradient arena.  The previous limits come back on return and on an exception.  False: nothing changes, no draw is consumed.
+    quad: train.py:406-407 `--quad`: the loss is multiplied by 4.0 behind the world_size factor (the loader is a `MosaicLoader(quad=True)`)."""
+    args = dict(locals())
+    if not multi_scale:
+        return _train(**args)
+    from .train_engine import set_plan_cache
+
+    core = de_parallel(model)
+    prev = set_plan_cache(core, max_plans=sys.maxsize, max_bytes=None)
+    try:
+        return _train(**args)
+    finally:
+        set_plan_cache(core, *prev)
+
+
+def _train(model, loader, hyp, epochs, device, batch_size, cos_lr, amp, ema, world_size, rank, optimizer_name, max_norm, start_epoch, on_batch_end, nbs,
+           val_loader, noval, sync_bn, overlap, autoanchor, imgsz, fused_optimizer, multi_scale, gs, quad):
+    from .torch_utils import multi_scale as resize_batch
     from .yolo import Segment
 
     seg = isinstance(de_parallel(model).model[-1], Segment)
@@ -129,6 +153,9 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
     hyp = dict(HYP_SCRATCH_LOW if hyp is None else hyp)
     device = torch.device(device) if device is not None else next(model.parameters()).device
     nb = len(loader)
+    if multi_scale:
+        ms_imgsz = imgsz or getattr(loader, "s", None) or 640
+        ms_gs = int(gs) if gs is not None else max(int(de_parallel(model).stride.max()), 32)   # train.py:219
     if batch_size is None:
         batch_size = int(next(iter(loader))[0].shape[0])
     total_batch = batch_size * world_size if rank != -1 else batch_size  # train.py works with the TOTAL batch size here
@@ -176,6 +203,8 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
                     g["lr"] = float(np.interp(ni, xi, [hyp["warmup_bias_lr"] if j == 0 else 0.0, g["initial_lr"] * lf(epoch)]))
                     if "momentum" in g:
                         g["momentum"] = float(np.interp(ni, xi, [hyp["warmup_momentum"], hyp["momentum"]]))
+            if multi_scale:                                                         # :392-398 (one draw per batch; sf == 1 leaves it alone)
+                imgs = resize_batch(imgs, ms_imgsz, ms_gs, torch.float16 if amp else torch.float32)
             if amp:   # fp16 plan: uint8 goes in as it is (the input kernel divides by 255), floats as fp16
                 x = imgs if imgs.dtype == torch.uint8 else imgs.half()
             else:     # fp32 plan (train.py without AMP): float32 images select it (train_engine.train_forward)
@@ -187,6 +216,8 @@ def train(model, loader, hyp=None, epochs=1, device=None, batch_size=None, cos_l
                 loss, loss_items = compute_loss(pred, targets.to(device))           # :400
             if rank != -1:
                 loss = loss * world_size                                            # :401-402
+            if quad:
+                loss = loss * 4.0                                                   # :406-407
             # the scale is FROZEN for all micro-batches of an accumulation window (GradScaler only changes it in update(), right after
             # an optimizer step, train.py:414): pending growth / back-off is applied below, behind zero_grad, never between two backwards
             (loss * scaler.scale).backward()                                        # :407

@@ -145,7 +145,7 @@ class BaseModel(nn.Module):
         """deepcopy / pickle (ModelEMA, train.py:469-488 checkpoints): engines hold ctypes handles and device plans -- they are
         per-process caches, not model state."""
         st = self.__dict__.copy()
-        for k in ("_engine_cache", "_train_engines", "_ddp_sink", "_ver_tensors"):
+        for k in ("_engine_cache", "_train_engines", "_train_arena", "_train_max_plans", "_train_max_bytes", "_ddp_sink", "_ver_tensors"):
             st.pop(k, None)
         return st
 
