@@ -663,7 +663,9 @@ int y5_bottleneck_fwd(const void* x, int ldx, const void* w1_packed, const float
                       int Kpad2, void* y, int ldy, int B, int H, int W, int C, int add, int max_blocks, void* stream);
 /* The last Bottleneck of a C3 + the C3's cv3 (models/common.py:246: cv3(cat(m(cv1(x)), cv2(x)))) as ONE launch: the Bottleneck's result
  * stays in LDS and is the first half of the 1x1's input, y2 (C3's cv2 output: NHWC slice, pixel stride ld2) the second; out (pixel stride
- * ldo, C3 <= 2 C channels) = act3(W3 [y ; y2] + b3) with W3 packed [2 C padded][Kpad3], k = (y's C channels, then y2's).  C = 32 (csrc/conv_bneck.h)
+ * ldo, C3 <= 2 C channels) = act3(W3 [y ; y2] + b3) with W3 packed [2 C padded][Kpad3], k = (y's C channels, then y2's).  At C = 32 the kernel reads
+ * all 64 rows of W3 and 64 entries of bias3 whatever C3 is (those of channels >= C3 reach no output): a filter packed for C3 <= 32 has 32 and must be
+ * padded by the caller; at C = 128 only the rows of C3 padded to 32 and the first C3 bias entries are read.  C = 32 (csrc/conv_bneck.h)
  * or C = 128 (csrc/conv_h3b.h CV3 form: cv3 as a GEMM-3 phase on the LDS-resident result; measured slower than two launches). */
 int y5_bottleneck_cv3_fwd(const void* x, int ldx, const void* w1_packed, const float* bias1, int Kpad1, const void* w2_packed, const float* bias2,
                           int Kpad2, const void* y2, int ld2, const void* w3_packed, const float* bias3, int Kpad3, int C3, int act3, void* out,

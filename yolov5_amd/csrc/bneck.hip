@@ -21,7 +21,8 @@ int launch_bneck(const Y5BneckParams& p, int max_blocks, hipStream_t stream) {
   const long long nwt = (long long)p.B * (p.H / 4) * (p.W / 8);
   const long long nbt = (nwt + NWV - 1) / NWV;
   long long G = max_blocks;
-  if (G <= 0) {
+  const bool own_grid = G <= 0;
+  if (own_grid) {
     const int num_cu = y5_num_cu();
     // resident workgroups per CU: LDS is the limit (52.5 KB at C = 32, one stage: three fit in 160 KB; the occupancy query answers two)
     int occ = (int)((160 * 1024) / lds);
@@ -33,7 +34,10 @@ int launch_bneck(const Y5BneckParams& p, int max_blocks, hipStream_t stream) {
   if (G >= 8) G &= ~7LL;
   //  the kernel assumes that only a workgroup's LAST tile can be the partial one; with the XCD remap that holds for grids that are a multiple
   // of eight or cover every tile -- an explicit cap of 1..7 below the tile count would put the partial block-tile mid-sequence
-  if (G < 8 && G < nbt && nbt >= 8 && nwt % NWV != 0) return y5_fail(Y5_ERR_UNSUPPORTED, "bottleneck: a grid cap below 8 needs a wave-tile count that is a multiple of the waves per workgroup");
+  if (G < 8 && G < nbt && nbt >= 8 && nwt % NWV != 0) {
+    if (!own_grid) return y5_fail(Y5_ERR_UNSUPPORTED, "bottleneck: a grid cap below 8 needs a wave-tile count that is a multiple of the waves per workgroup");
+    G = 8;   // the library's own choice (a CU budget below 8 workgroup slots) is never what gets refused: the smallest legal grid, min(nbt, 8) with nbt >= 8
+  }
   hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(NWV * 64), lds, stream, p);
   return y5_check_launch("y5_bottleneck_fwd");
 }

@@ -1057,6 +1057,8 @@ class Engine:
         (_g, (wp3, bp3, _K3, Kpad3, Npad3), stem3) = self._conv_weights(nxt)
         if stem3 is not None or Npad3 > 2 * x.C:
             return None
+        if x.C == 32 and Npad3 != 2 * x.C:   # conv_bneck.h reads all 2 C rows of the third filter and bias; a cv3 with <= 32 outputs is packed with 32
+            return None
         wp3, bp3 = self.be.from_torch(wp3), self.be.from_torch(bp3)
         y2 = _slice(cat, y.C, y.C)
         out = nxt["y"]
